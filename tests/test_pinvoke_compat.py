@@ -216,14 +216,14 @@ def test_stack_inits_and_setters():
     L.destroy(sid)
 
 
-def test_c_example_compiles_and_runs():
+def test_c_example_compiles_and_runs(tmp_path):
     """examples/pinvoke_bell.c builds against include/qrack_pinvoke_compat.h
     and links the extension .so directly — reference-style C code runs
     unchanged."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = "/tmp/qa_pinvoke_bell_test"
+    exe = str(tmp_path / "qa_pinvoke_bell_test")
     soname = os.path.basename(_SO)
     r = subprocess.run(
         ["gcc", os.path.join(root, "examples", "pinvoke_bell.c"),
