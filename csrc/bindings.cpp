@@ -41,7 +41,8 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
         .def("set_random_seed", &QI::SetRandomSeed)
         // ---- state access ----
         .def("set_permutation",
-            [](QI& q, bitCapInt perm) { q.SetPermutation(perm); })
+            [](QI& q, bitCapInt perm, C phase) { q.SetPermutation(perm, from_std<R>(phase)); },
+            py::arg("perm"), py::arg("phase") = C(1, 0))
         .def("get_amplitude", [](QI& q, bitCapInt i) { return to_std(q.GetAmplitude(i)); })
         .def("set_amplitude", [](QI& q, bitCapInt i, C a) { q.SetAmplitude(i, from_std<R>(a)); })
         .def("get_state_vector",
@@ -662,8 +663,10 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
                 DLDevice dev{};
 #ifdef QRACK_AMD_HIP_ENGINE
                 if (auto hip = std::dynamic_pointer_cast<QEngineHIP<R>>(q)) {
-                    hip->Finish();
+                    // DeviceBuffer() may queue the fill of a pending basis
+                    // state: take the pointer first, then drain the stream
                     data = (void*)(hip->DeviceBuffer() + offset);
+                    hip->Finish();
                     dev = { kDLROCM, hip->DeviceId() };
                 }
 #endif

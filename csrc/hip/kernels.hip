@@ -1875,14 +1875,31 @@ __device__ __forceinline__ void qftOrbitColumns(cplx<R>* v, R iSign, cplx<R> f0)
 // 16 consecutive lanes — the optimum for 8/16-byte LDS elements.
 __device__ __forceinline__ int qaSwz(int j) { return j ^ ((j >> 4) & 15); }
 
+// Value barrier for a synthesised amplitude: the optimiser must treat it
+// like a loaded one. Seeing the select, it folds the known zeros into the
+// orbit arithmetic and contracts the rest into different FMAs than the
+// normal kernel's, and the stores are then no longer bit-identical to it.
+template <typename R> __device__ __forceinline__ cplx<R> qaOpaque(cplx<R> a)
+{
+    asm volatile("" : "+v"(a.re), "+v"(a.im));
+    return a;
+}
+
 // One group of K columns applied over a 2^tb-amplitude tile as 16-amp
 // register orbits. K is a template parameter so v[] stays in registers
 // (runtime K forces the array to scratch — measured 2.5x slower). Groups
 // with gLo >= 6 may read/write HBM directly (lane-contiguous within the
 // orbit slot loops); gLo < 6 groups always go through (swizzled) LDS.
-template <typename R, int K, bool PRE>
+//
+// BASIS: the source is the basis state phase·|perm> and the buffer contents
+// are undefined — a fromGlobal gather synthesises its values from the index
+// (idxBase = the tile's first global index) instead of loading them; the
+// arithmetic, zeros included, is unchanged. SUMS: a toGlobal scatter also
+// adds the norm of every amplitude it stores into `acc`.
+template <typename R, int K, bool PRE, bool BASIS = false, bool SUMS = false>
 __device__ __forceinline__ void qftLowGroup(cplx<R>* svBase, cplx<R>* lds, int tile, int gLo,
-    R scaleHi, R iSign, bool fromGlobal, bool toGlobal)
+    R scaleHi, R iSign, bool fromGlobal, bool toGlobal, bitCapInt idxBase = 0u,
+    bitCapInt perm = 0u, cplx<R> phase = cplx<R>{ (R)0, (R)0 }, double* acc = nullptr)
 {
     constexpr int NS = 1 << K;
     const int orbitCount = tile >> K;
@@ -1891,8 +1908,17 @@ __device__ __forceinline__ void qftLowGroup(cplx<R>* svBase, cplx<R>* lds, int t
         const int r = ((o >> gLo) << (gLo + K)) | below;
         cplx<R> v[NS];
         if (fromGlobal) {
+            if (BASIS) {
 #pragma unroll
-            for (int b = 0; b < NS; ++b) v[b] = svBase[r | (b << gLo)];
+                for (int b = 0; b < NS; ++b) {
+                    v[b] = qaOpaque<R>(((idxBase | (bitCapInt)(r | (b << gLo))) == perm)
+                            ? phase
+                            : cplx<R>{ (R)0, (R)0 });
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) v[b] = svBase[r | (b << gLo)];
+            }
         } else {
 #pragma unroll
             for (int b = 0; b < NS; ++b) v[b] = lds[qaSwz(r | (b << gLo))];
@@ -1903,6 +1929,10 @@ __device__ __forceinline__ void qftLowGroup(cplx<R>* svBase, cplx<R>* lds, int t
         if (toGlobal) {
 #pragma unroll
             for (int b = 0; b < NS; ++b) svBase[r | (b << gLo)] = v[b];
+            if (SUMS) {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) *acc += (double)norm(v[b]);
+            }
         } else {
 #pragma unroll
             for (int b = 0; b < NS; ++b) lds[qaSwz(r | (b << gLo))] = v[b];
@@ -1961,6 +1991,87 @@ __global__ void __launch_bounds__(256, 3)
     }
 }
 
+// k_qft_low_lds with a synthesised source and/or a norm epilogue. The loop
+// is the normal kernel's, repeated here rather than shared through a
+// device function so the normal kernel compiles exactly as before.
+// BASIS: first pass of a ladder whose source is the basis state
+// phase·|perm> — the state is synthesised from the index instead of read
+// (the buffer holds nothing defined yet); the stores are bit-identical to
+// the normal kernel's. SUMS: also leaves tileSums[t] = sum of |amp|^2 over
+// the 2^tb amplitudes of tile t, taken from the values it stores.
+template <typename R, int K, bool PRE, bool BASIS, bool SUMS>
+__global__ void __launch_bounds__(256, 3) k_qft_low_lds_var(cplx<R>* sv, bitCapInt nTiles, int tb,
+    int colMax, R piSign, bitCapInt perm, cplx<R> phase, double* tileSums)
+{
+    // REQUIRES colMax+1 to be a multiple of K (the engine aligns the ladder
+    // length; K = 4 fp32 / 3 fp64) so every group is the single kernel-wide
+    // instantiation — keeps the orbit registers allocated without spills.
+    extern __shared__ unsigned char qa_lds_raw[];
+    cplx<R>* lds = reinterpret_cast<cplx<R>*>(qa_lds_raw);
+    const int tile = 1 << tb;
+    const int nCols = colMax + 1;
+    const int nG = nCols / K;
+    const R iSign = (piSign >= 0) ? (R)1 : (R)-1;
+    // a group may touch HBM directly only if its orbit slot loops are
+    // lane-contiguous, i.e. gLo >= 6; otherwise a contiguous LDS<->HBM
+    // copy brackets the ladder on that side
+    const int firstG = PRE ? 0 : (nG - 1);
+    const int lastG = PRE ? (nG - 1) : 0;
+    const bool copyIn = (K * firstG) < 6;
+    const bool copyOut = (K * lastG) < 6;
+    for (bitCapInt t = blockIdx.x; t < nTiles; t += gridDim.x) {
+        cplx<R>* svBase = sv + (t << tb);
+        const bitCapInt idxBase = t << tb;
+        double acc = 0;
+        if (copyIn) {
+            if (BASIS) {
+                for (int j = threadIdx.x; j < tile; j += blockDim.x) {
+                    lds[qaSwz(j)] =
+                        ((idxBase | (bitCapInt)j) == perm) ? phase : cplx<R>{ (R)0, (R)0 };
+                }
+            } else {
+                for (int j = threadIdx.x; j < tile; j += blockDim.x) lds[qaSwz(j)] = svBase[j];
+            }
+        }
+        for (int gi = 0; gi < nG; ++gi) {
+            const int g = PRE ? gi : (nG - 1 - gi);
+            const int gLo = K * g;
+            const bool fromGlobal = (gi == 0) && !copyIn;
+            const bool toGlobal = (gi == nG - 1) && !copyOut;
+            const R scaleHi = piSign / (R)(1 << (gLo + K - 1));
+            if (gi != 0 || copyIn) __syncthreads();
+            qftLowGroup<R, K, PRE, BASIS, SUMS>(svBase, lds, tile, gLo, scaleHi, iSign,
+                fromGlobal, toGlobal, idxBase, perm, phase, &acc);
+        }
+        if (copyOut) {
+            __syncthreads();
+            if (SUMS) {
+                for (int j = threadIdx.x; j < tile; j += blockDim.x) {
+                    const cplx<R> a = lds[qaSwz(j)];
+                    svBase[j] = a;
+                    acc += (double)norm(a);
+                }
+            } else {
+                for (int j = threadIdx.x; j < tile; j += blockDim.x) svBase[j] = lds[qaSwz(j)];
+            }
+        }
+        if (SUMS) {
+            // fixed-order block reduction: wave shuffle tree, then the
+            // waves in index order — one double per tile, no atomics
+            __shared__ double waveSums[QA_BLOCK / 64];
+            acc = waveReduceSum(acc);
+            if ((threadIdx.x & 63) == 0) waveSums[threadIdx.x >> 6] = acc;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                double s = 0;
+                for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += waveSums[w];
+                tileSums[t] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 template <typename R>
 void launchQftLowLds(
     cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, int sign, bool pre, hipStream_t stream)
@@ -1979,14 +2090,50 @@ void launchQftLowLds(
     }
 }
 
+template <typename R>
+void launchQftLowLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, int sign, bool pre,
+    bitCapInt perm, cplx<R> phase, hipStream_t stream)
+{
+    constexpr int K = qaLowLadderK<R>();
+    const bitCapInt nTiles = maxQPower >> tb;
+    const size_t ldsBytes = (size_t(1) << tb) * sizeof(cplx<R>);
+    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const R piSign = (R)sign * (R)3.14159265358979323846;
+    if (pre) {
+        hipLaunchKernelGGL((k_qft_low_lds_var<R, K, true, true, false>), dim3(grid),
+            dim3(QA_BLOCK), ldsBytes, stream, sv, nTiles, tb, colMax, piSign, perm, phase,
+            (double*)nullptr);
+    } else {
+        hipLaunchKernelGGL((k_qft_low_lds_var<R, K, false, true, false>), dim3(grid),
+            dim3(QA_BLOCK), ldsBytes, stream, sv, nTiles, tb, colMax, piSign, perm, phase,
+            (double*)nullptr);
+    }
+}
+
+template <typename R>
+void launchQftLowLdsSums(cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, double* tileSumsDev,
+    hipStream_t stream)
+{
+    constexpr int K = qaLowLadderK<R>();
+    const bitCapInt nTiles = maxQPower >> tb;
+    const size_t ldsBytes = (size_t(1) << tb) * sizeof(cplx<R>);
+    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const R piSign = (R)3.14159265358979323846;
+    hipLaunchKernelGGL((k_qft_low_lds_var<R, K, false, false, true>), dim3(grid), dim3(QA_BLOCK),
+        ldsBytes, stream, sv, nTiles, tb, colMax, piSign, (bitCapInt)0u, cplx<R>{ (R)0, (R)0 },
+        tileSumsDev);
+}
+
 // One group of K mid columns over a 64 x 2^nCols 2D tile as 16-amp register
 // orbits (K templated — see qftLowGroup). Every access, LDS or HBM, keeps
 // the 64-value `low` dimension in the lane index, so loads/stores are
 // 512 B-contiguous per slot and LDS is bank-conflict-free without swizzle.
-template <typename R, int K, bool PRE>
+// BASIS: as in qftLowGroup — a fromGlobal gather is synthesised from the
+// index of the basis state phase·|perm> instead of loaded.
+template <typename R, int K, bool PRE, bool BASIS = false>
 __device__ __forceinline__ void qftMidGroup(cplx<R>* sv, cplx<R>* lds, bitCapInt xBase,
     int colLo, int tileAmps, int gLo, R midFixed, R hbScale, R scaleHi, R iSign,
-    bool fromGlobal, bool toGlobal)
+    bool fromGlobal, bool toGlobal, bitCapInt perm = 0u, cplx<R> phase = cplx<R>{ (R)0, (R)0 })
 {
     constexpr int NS = 1 << K;
     const int orbitCount = tileAmps >> K;
@@ -1997,9 +2144,19 @@ __device__ __forceinline__ void qftMidGroup(cplx<R>* sv, cplx<R>* lds, bitCapInt
         const int cb0 = ((cbr >> gLo) << (gLo + K)) | cbBelow;
         cplx<R> v[NS];
         if (fromGlobal) {
+            if (BASIS) {
 #pragma unroll
-            for (int b = 0; b < NS; ++b) {
-                v[b] = sv[xBase | ((bitCapInt)(cb0 | (b << gLo)) << colLo) | (bitCapInt)low];
+                for (int b = 0; b < NS; ++b) {
+                    v[b] = qaOpaque<R>(
+                        ((xBase | ((bitCapInt)(cb0 | (b << gLo)) << colLo) | (bitCapInt)low) == perm)
+                            ? phase
+                            : cplx<R>{ (R)0, (R)0 });
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) {
+                    v[b] = sv[xBase | ((bitCapInt)(cb0 | (b << gLo)) << colLo) | (bitCapInt)low];
+                }
             }
         } else {
 #pragma unroll
@@ -2061,6 +2218,40 @@ __global__ void __launch_bounds__(256, 3)
     }
 }
 
+// k_qft_mid_lds as the first pass from the basis state phase·|perm> (see
+// k_qft_low_lds_var): write-only, stores bit-identical to the normal kernel
+template <typename R, int K, bool PRE>
+__global__ void __launch_bounds__(256, 3) k_qft_mid_lds_basis(
+    cplx<R>* sv, bitCapInt nTiles, int colLo, int nCols, R piSign, bitCapInt perm, cplx<R> phase)
+{
+    // REQUIRES nCols to be a multiple of K (launcher picks K) so every
+    // group is the single kernel-wide instantiation — no register spills.
+    extern __shared__ unsigned char qa_lds_raw2[];
+    cplx<R>* lds = reinterpret_cast<cplx<R>*>(qa_lds_raw2);
+    const int C = 1 << nCols;
+    const int tileAmps = 64 * C;
+    const int nG = nCols / K;
+    const bitCapInt midMask = (ONE_BCI << (colLo - 6)) - 1u;
+    const R hbScale = (R)(uint64_t)(ONE_BCI << colLo);
+    const R iSign = (piSign >= 0) ? (R)1 : (R)-1;
+    for (bitCapInt t = blockIdx.x; t < nTiles; t += gridDim.x) {
+        const bitCapInt xBase =
+            ((t >> (colLo - 6)) << (colLo + nCols)) | ((t & midMask) << 6);
+        const R midFixed = (R)(uint64_t)((t & midMask) << 6);
+        for (int gi = 0; gi < nG; ++gi) {
+            const int g = PRE ? gi : (nG - 1 - gi);
+            const int gLo = K * g;
+            const bool fromGlobal = (gi == 0);
+            const bool toGlobal = (gi == nG - 1);
+            const R scaleHi = piSign / (R)(ONE_BCI << (colLo + gLo + K - 1));
+            if (gi != 0) __syncthreads();
+            qftMidGroup<R, K, PRE, true>(sv, lds, xBase, colLo, tileAmps, gLo, midFixed, hbScale,
+                scaleHi, iSign, fromGlobal, toGlobal, perm, phase);
+        }
+        __syncthreads();
+    }
+}
+
 template <typename R>
 void launchQftMidLds(
     cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols, int sign, bool pre, hipStream_t stream)
@@ -2095,6 +2286,40 @@ void launchQftMidLds(
             hipLaunchKernelGGL((k_qft_mid_lds<R, 2, false>), dim3(grid), dim3(QA_BLOCK), ldsBytes,
                 stream, sv, nTiles, colLo, nCols, piSign);
         }
+    }
+}
+
+template <typename R, int K>
+static void launchQftMidLdsBasisK(cplx<R>* sv, bitCapInt nTiles, int grid, size_t ldsBytes,
+    int colLo, int nCols, R piSign, bool pre, bitCapInt perm, cplx<R> phase, hipStream_t stream)
+{
+    if (pre) {
+        hipLaunchKernelGGL((k_qft_mid_lds_basis<R, K, true>), dim3(grid), dim3(QA_BLOCK), ldsBytes,
+            stream, sv, nTiles, colLo, nCols, piSign, perm, phase);
+    } else {
+        hipLaunchKernelGGL((k_qft_mid_lds_basis<R, K, false>), dim3(grid), dim3(QA_BLOCK),
+            ldsBytes, stream, sv, nTiles, colLo, nCols, piSign, perm, phase);
+    }
+}
+
+template <typename R>
+void launchQftMidLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols, int sign,
+    bool pre, bitCapInt perm, cplx<R> phase, hipStream_t stream)
+{
+    const bitCapInt nTiles = maxQPower >> (6 + nCols);
+    const size_t ldsBytes = (size_t(64) << nCols) * sizeof(cplx<R>);
+    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const R piSign = (R)sign * (R)3.14159265358979323846;
+    // same group-width choice as launchQftMidLds
+    if ((nCols & 3) == 0) {
+        launchQftMidLdsBasisK<R, 4>(
+            sv, nTiles, grid, ldsBytes, colLo, nCols, piSign, pre, perm, phase, stream);
+    } else if ((nCols % 3) == 0) {
+        launchQftMidLdsBasisK<R, 3>(
+            sv, nTiles, grid, ldsBytes, colLo, nCols, piSign, pre, perm, phase, stream);
+    } else {
+        launchQftMidLdsBasisK<R, 2>(
+            sv, nTiles, grid, ldsBytes, colLo, nCols, piSign, pre, perm, phase, stream);
     }
 }
 
@@ -2819,6 +3044,37 @@ void launchChunkSums(
         (k_chunk_sums<R>), dim3((uint32_t)nChunks), dim3(QA_BLOCK), 0, stream, sv, chunkLen, sumsDev);
 }
 
+// chunk sums from the per-tile sums a SUMS low-ladder pass left behind:
+// one wave per chunk, each lane adds its strided share in index order, then
+// the fixed wave shuffle tree — deterministic
+__global__ void k_tile_chunk_sums(const double* tileSums, bitCapInt tilesPerChunk, double* sums)
+{
+    const double* src = tileSums + (bitCapInt)blockIdx.x * tilesPerChunk;
+    double s = 0;
+    for (bitCapInt j = threadIdx.x; j < tilesPerChunk; j += 64u) s += src[j];
+    s = waveReduceSum(s);
+    if (threadIdx.x == 0) sums[blockIdx.x] = s;
+}
+
+void launchTileChunkSums(const double* tileSumsDev, bitCapInt nChunks, bitCapInt tilesPerChunk,
+    double* sumsDev, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_tile_chunk_sums, dim3((uint32_t)nChunks), dim3(64), 0, stream,
+        tileSumsDev, tilesPerChunk, sumsDev);
+}
+
+// sv[perm] = amp (the one non-zero amplitude of a basis state)
+template <typename R> __global__ void k_set_amp(cplx<R>* sv, bitCapInt perm, cplx<R> amp)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) sv[perm] = amp;
+}
+
+template <typename R>
+void launchSetAmp(cplx<R>* sv, bitCapInt perm, cplx<R> amp, hipStream_t stream)
+{
+    hipLaunchKernelGGL((k_set_amp<R>), dim3(1), dim3(1), 0, stream, sv, perm, amp);
+}
+
 template <typename R>
 __global__ void k_inner(
     const cplx<R>* a, const cplx<R>* b, bitCapInt maxI, double* partialsRe, double* partialsIm)
@@ -2959,6 +3215,12 @@ void launchPartProbs(const cplx<R>* sv, bitCapInt maxQPower, bitLenInt start, bi
     template void launchMtrx2qPair2<R>(cplx<R>*, const Gate4x4Pair2Args<R>&, hipStream_t);         \
     template void launchQftLowLds<R>(cplx<R>*, bitCapInt, int, int, int, bool, hipStream_t);        \
     template void launchQftMidLds<R>(cplx<R>*, bitCapInt, int, int, int, bool, hipStream_t);        \
+    template void launchQftLowLdsBasis<R>(                                                          \
+        cplx<R>*, bitCapInt, int, int, int, bool, bitCapInt, cplx<R>, hipStream_t);                 \
+    template void launchQftLowLdsSums<R>(cplx<R>*, bitCapInt, int, int, double*, hipStream_t);      \
+    template void launchQftMidLdsBasis<R>(                                                          \
+        cplx<R>*, bitCapInt, int, int, int, bool, bitCapInt, cplx<R>, hipStream_t);                 \
+    template void launchSetAmp<R>(cplx<R>*, bitCapInt, cplx<R>, hipStream_t);                       \
     template void launchQftColumn2General<R>(cplx<R>*, bitCapInt, bitCapInt, bitCapInt,            \
         const RampArgs&, double, double, bool, hipStream_t);                                        \
     template void launchQftColumnTopRange<R>(cplx<R>*, bitCapInt, const RampArgs&, double, bool,    \

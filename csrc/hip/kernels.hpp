@@ -212,6 +212,34 @@ template <typename R>
 void launchQftMidLds(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols, int sign, bool pre,
     hipStream_t stream);
 
+// "source is a basis state" variants of the two LDS passes: the buffer's
+// contents are undefined and the first gather is synthesised as
+// index == perm ? phase : 0 — a write-only pass whose stores are
+// bit-identical to the normal kernel run on the materialised basis state
+template <typename R>
+void launchQftLowLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, int sign, bool pre,
+    bitCapInt perm, cplx<R> phase, hipStream_t stream);
+
+template <typename R>
+void launchQftMidLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols, int sign,
+    bool pre, bitCapInt perm, cplx<R> phase, hipStream_t stream);
+
+// forward low ladder that also writes tileSumsDev[t] = sum |amp|^2 of the
+// 2^tb amplitudes it stored for tile t (maxQPower >> tb doubles; fixed
+// reduction order, no atomics)
+template <typename R>
+void launchQftLowLdsSums(cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, double* tileSumsDev,
+    hipStream_t stream);
+
+// sums[c] = tileSums[c*tilesPerChunk .. (c+1)*tilesPerChunk) added in a
+// fixed order — replaces launchChunkSums when tile sums are valid
+void launchTileChunkSums(const double* tileSumsDev, bitCapInt nChunks, bitCapInt tilesPerChunk,
+    double* sumsDev, hipStream_t stream);
+
+// sv[perm] = amp from a one-thread kernel (no host staging, no sync)
+template <typename R>
+void launchSetAmp(cplx<R>* sv, bitCapInt perm, cplx<R> amp, hipStream_t stream);
+
 // generic K-column fused QFT pass (2^K-amplitude orbits; K=4 instantiated)
 template <typename R>
 void launchQftColumnK(cplx<R>* sv, bitCapInt maxQPower, bitLenInt rampStart, bitLenInt col,

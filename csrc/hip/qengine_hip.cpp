@@ -140,7 +140,7 @@ QEngineHIP<R>::QEngineHIP(bitLenInt qBitCount, bitCapInt initState, RngPtr rgp, 
     deviceId = (devId < 0) ? tracker.defaultDevice() : (int)devId;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     QA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    dState = allocDev(maxQPower);
+    dState_ = allocDev(maxQPower);
     const int maxGrid = QA_REDUCE_MAX_BLOCKS;
     QA_HIP_CHECK(hipMalloc(&dPartials, maxGrid * 2 * sizeof(double)));
     QA_HIP_CHECK(hipMalloc(&dIdx, maxGrid * sizeof(bitCapInt)));
@@ -151,8 +151,9 @@ QEngineHIP<R>::QEngineHIP(bitLenInt qBitCount, bitCapInt initState, RngPtr rgp, 
 template <typename R> QEngineHIP<R>::~QEngineHIP()
 {
     hipStreamSynchronize(stream);
-    if (dState) freeDev(dState, maxQPower);
+    if (dState_) freeDev(dState_, maxQPower);
     releaseScratch();
+    releaseTileSums();
     if (dPartials) hipFree(dPartials);
     if (dIdx) hipFree(dIdx);
     hipStreamDestroy(stream);
@@ -194,14 +195,82 @@ template <typename R> void QEngineHIP<R>::releaseScratch()
     }
 }
 
-template <typename R> void QEngineHIP<R>::swapScratch() { std::swap(dState, dScratch); }
+template <typename R> void QEngineHIP<R>::swapScratch()
+{
+    // the scratch buffer holds the new state: whatever described the old
+    // buffer no longer applies
+    basisPending_ = false;
+    tileSumsValid_ = false;
+    std::swap(dState_, dScratch);
+}
 
 template <typename R> void QEngineHIP<R>::resizeState(bitCapInt nAmps, cplx<R>* newBuf)
 {
     Finish();
     releaseScratch();
-    freeDev(dState, maxQPower);
-    dState = newBuf;
+    freeDev(dState_, maxQPower);
+    setStateBuffer(newBuf);
+}
+
+template <typename R> void QEngineHIP<R>::setStateBuffer(cplx<R>* buf)
+{
+    dState_ = buf;
+    basisPending_ = false;
+    // the tile-sum buffer is sized by the state: drop it with the old one
+    releaseTileSums();
+}
+
+template <typename R> void QEngineHIP<R>::releaseTileSums()
+{
+    if (dTileSums_) hipFree(dTileSums_);
+    dTileSums_ = nullptr;
+    tileSumsLen_ = 0;
+    tileSumsValid_ = false;
+}
+
+template <typename R> double* QEngineHIP<R>::tileSumsBuffer()
+{
+    const bitCapInt len = maxQPower >> qaLdsTileBits<R>();
+    if (dTileSums_ && tileSumsLen_ != len) releaseTileSums();
+    if (!dTileSums_) {
+        QA_HIP_CHECK(hipMalloc(&dTileSums_, len * sizeof(double)));
+        tileSumsLen_ = len;
+    }
+    return dTileSums_;
+}
+
+namespace {
+bool qaEnvSwitch(const char* name)
+{
+    const char* env = std::getenv(name);
+    return env ? std::atoi(env) != 0 : true;
+}
+// QRACK_GPU_QFT_LAZYPERM=0: SetPermutation fills the buffer eagerly
+bool qaLazyPerm()
+{
+    static const bool v = qaEnvSwitch("QRACK_GPU_QFT_LAZYPERM");
+    return v;
+}
+// QRACK_GPU_QFT_SUMS=0: sampling always re-reads the state for its chunk sums
+bool qaQftSums()
+{
+    static const bool v = qaEnvSwitch("QRACK_GPU_QFT_SUMS");
+    return v;
+}
+} // namespace
+
+template <typename R> bool QEngineHIP<R>::tileSumsUsable() const
+{
+    return qaQftSums() && !externView_;
+}
+
+template <typename R> void QEngineHIP<R>::materialize()
+{
+    if (!basisPending_) return;
+    basisPending_ = false;
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    QA_HIP_CHECK(hipMemsetAsync(dState_, 0, sizeof(cplx<R>) * maxQPower, stream));
+    launchSetAmp<R>(dState_, basisPerm_, basisPhase_, stream);
 }
 
 template <typename R> void QEngineHIP<R>::SetDevice(int64_t devId)
@@ -212,14 +281,15 @@ template <typename R> void QEngineHIP<R>::SetDevice(int64_t devId)
     std::vector<cplx<R>> host(maxQPower);
     GetQuantumState(host.data());
     releaseScratch();
-    freeDev(dState, maxQPower);
+    releaseTileSums();
+    freeDev(dState_, maxQPower);
     hipStreamDestroy(stream);
     hipFree(dPartials);
     hipFree(dIdx);
     deviceId = (int)devId;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     QA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    dState = allocDev(maxQPower);
+    dState_ = allocDev(maxQPower);
     QA_HIP_CHECK(hipMalloc(&dPartials, QA_REDUCE_MAX_BLOCKS * 2 * sizeof(double)));
     QA_HIP_CHECK(hipMalloc(&dIdx, QA_REDUCE_MAX_BLOCKS * sizeof(bitCapInt)));
     SetQuantumState(host.data());
@@ -231,7 +301,7 @@ template <typename R> void QEngineHIP<R>::SetQuantumState(const cplx<R>* inputSt
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
     QA_HIP_CHECK(hipMemcpyAsync(
-        dState, inputState, sizeof(cplx<R>) * maxQPower, hipMemcpyHostToDevice, stream));
+        wStateAll(), inputState, sizeof(cplx<R>) * maxQPower, hipMemcpyHostToDevice, stream));
     Finish();
     runningNorm = (R)-1;
 }
@@ -240,7 +310,7 @@ template <typename R> void QEngineHIP<R>::GetQuantumState(cplx<R>* outputState)
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
     QA_HIP_CHECK(hipMemcpyAsync(
-        outputState, dState, sizeof(cplx<R>) * maxQPower, hipMemcpyDeviceToHost, stream));
+        outputState, rState(), sizeof(cplx<R>) * maxQPower, hipMemcpyDeviceToHost, stream));
     Finish();
 }
 
@@ -249,7 +319,7 @@ template <typename R> cplx<R> QEngineHIP<R>::GetAmplitude(bitCapInt perm)
     cplx<R> amp;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     QA_HIP_CHECK(
-        hipMemcpyAsync(&amp, dState + perm, sizeof(cplx<R>), hipMemcpyDeviceToHost, stream));
+        hipMemcpyAsync(&amp, rState() + perm, sizeof(cplx<R>), hipMemcpyDeviceToHost, stream));
     Finish();
     return amp;
 }
@@ -258,24 +328,34 @@ template <typename R> void QEngineHIP<R>::SetAmplitude(bitCapInt perm, cplx<R> a
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
     QA_HIP_CHECK(
-        hipMemcpyAsync(dState + perm, &amp, sizeof(cplx<R>), hipMemcpyHostToDevice, stream));
+        hipMemcpyAsync(wState() + perm, &amp, sizeof(cplx<R>), hipMemcpyHostToDevice, stream));
     Finish();
     runningNorm = (R)-1;
 }
 
 template <typename R> void QEngineHIP<R>::SetPermutation(bitCapInt perm, cplx<R> phase)
 {
-    QA_HIP_CHECK(hipSetDevice(deviceId));
-    QA_HIP_CHECK(hipMemsetAsync(dState, 0, sizeof(cplx<R>) * maxQPower, stream));
     if (norm(phase) <= 0) phase = cplx<R>(1, 0);
-    SetAmplitude(perm, phase);
+    if (qaLazyPerm()) {
+        // lazy: record "the state is phase·|perm>" and touch nothing; the
+        // first reader/writer materialises it, a QFT whose first pass is an
+        // LDS kernel synthesises it instead
+        basisPending_ = true;
+        basisPerm_ = perm;
+        basisPhase_ = phase;
+        tileSumsValid_ = false;
+    } else {
+        QA_HIP_CHECK(hipSetDevice(deviceId));
+        QA_HIP_CHECK(hipMemsetAsync(wStateAll(), 0, sizeof(cplx<R>) * maxQPower, stream));
+        SetAmplitude(perm, phase);
+    }
     runningNorm = (R)1;
 }
 
 template <typename R> void QEngineHIP<R>::ZeroAmplitudes()
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    QA_HIP_CHECK(hipMemsetAsync(dState, 0, sizeof(cplx<R>) * maxQPower, stream));
+    QA_HIP_CHECK(hipMemsetAsync(wStateAll(), 0, sizeof(cplx<R>) * maxQPower, stream));
     runningNorm = 0;
 }
 
@@ -284,9 +364,10 @@ template <typename R> void QEngineHIP<R>::CopyStateVec(QEnginePtr<R> src)
     QEngineHIP<R>* o = dynamic_cast<QEngineHIP<R>*>(src.get());
     QA_HIP_CHECK(hipSetDevice(deviceId));
     if (o && o->deviceId == deviceId) {
+        const cplx<R>* srcBuf = o->rState();
         o->Finish();
         QA_HIP_CHECK(hipMemcpyAsync(
-            dState, o->dState, sizeof(cplx<R>) * maxQPower, hipMemcpyDeviceToDevice, stream));
+            wStateAll(), srcBuf, sizeof(cplx<R>) * maxQPower, hipMemcpyDeviceToDevice, stream));
         Finish();
     } else {
         std::vector<cplx<R>> host(maxQPower);
@@ -308,7 +389,7 @@ void QEngineHIP<R>::GetAmplitudePage(cplx<R>* pagePtr, bitCapInt offset, bitCapI
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
     QA_HIP_CHECK(hipMemcpyAsync(
-        pagePtr, dState + offset, sizeof(cplx<R>) * length, hipMemcpyDeviceToHost, stream));
+        pagePtr, rState() + offset, sizeof(cplx<R>) * length, hipMemcpyDeviceToHost, stream));
     Finish();
 }
 
@@ -317,7 +398,7 @@ void QEngineHIP<R>::SetAmplitudePage(const cplx<R>* pagePtr, bitCapInt offset, b
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
     QA_HIP_CHECK(hipMemcpyAsync(
-        dState + offset, pagePtr, sizeof(cplx<R>) * length, hipMemcpyHostToDevice, stream));
+        wState() + offset, pagePtr, sizeof(cplx<R>) * length, hipMemcpyHostToDevice, stream));
     Finish();
     runningNorm = (R)-1;
 }
@@ -329,12 +410,13 @@ void QEngineHIP<R>::SetAmplitudePage(
     QEngineHIP<R>* o = dynamic_cast<QEngineHIP<R>*>(pageEnginePtr.get());
     QA_HIP_CHECK(hipSetDevice(deviceId));
     if (o) {
+        const cplx<R>* srcBuf = o->rState();
         o->Finish();
         if (o->deviceId == deviceId) {
-            QA_HIP_CHECK(hipMemcpyAsync(dState + dstOffset, o->dState + srcOffset,
+            QA_HIP_CHECK(hipMemcpyAsync(wState() + dstOffset, srcBuf + srcOffset,
                 sizeof(cplx<R>) * length, hipMemcpyDeviceToDevice, stream));
         } else {
-            QA_HIP_CHECK(hipMemcpyPeerAsync(dState + dstOffset, deviceId, o->dState + srcOffset,
+            QA_HIP_CHECK(hipMemcpyPeerAsync(wState() + dstOffset, deviceId, srcBuf + srcOffset,
                 o->deviceId, sizeof(cplx<R>) * length, stream));
         }
         Finish();
@@ -351,21 +433,23 @@ template <typename R> void QEngineHIP<R>::ShuffleBuffers(QEnginePtr<R> engine)
     QEngineHIP<R>* o = dynamic_cast<QEngineHIP<R>*>(engine.get());
     const bitCapInt half = maxQPower >> 1u;
     if (o && o->deviceId == deviceId) {
+        cplx<R>* oBuf = o->wState();
         o->Finish();
         QA_HIP_CHECK(hipSetDevice(deviceId));
-        launchShuffleSwap<R>(dState + half, o->dState, half, stream);
+        launchShuffleSwap<R>(wState() + half, oBuf, half, stream);
         Finish();
     } else if (o) {
         // cross-device in-process: stage through a temp on this device
+        cplx<R>* oBuf = o->wState();
         o->Finish();
         QA_HIP_CHECK(hipSetDevice(deviceId));
         cplx<R>* tmp = allocDev(half);
         QA_HIP_CHECK(hipMemcpyAsync(
-            tmp, dState + half, sizeof(cplx<R>) * half, hipMemcpyDeviceToDevice, stream));
+            tmp, wState() + half, sizeof(cplx<R>) * half, hipMemcpyDeviceToDevice, stream));
         QA_HIP_CHECK(hipMemcpyPeerAsync(
-            dState + half, deviceId, o->dState, o->deviceId, sizeof(cplx<R>) * half, stream));
+            wState() + half, deviceId, oBuf, o->deviceId, sizeof(cplx<R>) * half, stream));
         QA_HIP_CHECK(hipMemcpyPeerAsync(
-            o->dState, o->deviceId, tmp, deviceId, sizeof(cplx<R>) * half, stream));
+            oBuf, o->deviceId, tmp, deviceId, sizeof(cplx<R>) * half, stream));
         Finish();
         freeDev(tmp, half);
     } else {
@@ -406,7 +490,7 @@ void QEngineHIP<R>::Apply2x2(bitCapInt offset1, bitCapInt offset2, const cplx<R>
     GateArgs<R> a = makeGateArgs(offset1, offset2, mtrx, qPowersSorted);
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("apply2x2", stream);
-    launchApply2x2<R>(dState, a, stream);
+    launchApply2x2<R>(wState(), a, stream);
 }
 
 // general two-qubit 4x4 apply: one pass (k_mtrx_2q).
@@ -429,7 +513,7 @@ void QEngineHIP<R>::Mtrx2q(const cplx<R>* m, bitLenInt q1, bitLenInt q2)
     a.maxI = maxQPower >> 2u;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("mtrx_2q", stream);
-    launchMtrx2q<R>(dState, a, stream);
+    launchMtrx2q<R>(wState(), a, stream);
 }
 
 // batched disjoint two-qubit 4x4 layer: in-tile pairs fuse through the LDS
@@ -480,7 +564,7 @@ void QEngineHIP<R>::Mtrx2qBatch(const std::vector<cplx<R>>& ms,
         a.k = (int)k;
         a.maxQPower = maxQPower;
         HipProfScope prof("mtrx_2q_batch_lds", stream);
-        launchMtrx2qBatchLds<R>(dState, a, stream);
+        launchMtrx2qBatchLds<R>(wState(), a, stream);
         i += k;
     }
     // the rest: TWO disjoint 4x4s per pass (16-amplitude orbits)
@@ -499,7 +583,7 @@ void QEngineHIP<R>::Mtrx2qBatch(const std::vector<cplx<R>>& ms,
         for (int b = 0; b < 4; ++b) a.sorted4[b] = s4[b];
         a.orbits = maxQPower >> 4u;
         HipProfScope prof("mtrx_2q_pair2", stream);
-        launchMtrx2qPair2<R>(dState, a, stream);
+        launchMtrx2qPair2<R>(wState(), a, stream);
     }
     for (; j < rest.size(); ++j) {
         const size_t ix = rest[j];
@@ -556,7 +640,7 @@ void QEngineHIP<R>::FSimBatch(const std::vector<R>& thetas, const std::vector<R>
         a.k = (int)k;
         a.maxQPower = maxQPower;
         HipProfScope prof("fsim_batch_lds", stream);
-        launchMtrx2qBatchLds<R>(dState, a, stream);
+        launchMtrx2qBatchLds<R>(wState(), a, stream);
         i += k;
     }
     if (!rest.empty()) {
@@ -605,7 +689,7 @@ void QEngineHIP<R>::CPhasePairs(const std::vector<bitLenInt>& controls,
     a.maxI = maxQPower;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("cphase_pairs", stream);
-    launchCPhasePairs<R>(dState, a, stream);
+    launchCPhasePairs<R>(wState(), a, stream);
 }
 
 // batched disjoint CNOTs: one permutation pass per layer (k_cnot_batch).
@@ -636,7 +720,7 @@ void QEngineHIP<R>::CnotBatch(
     a.maxI = maxQPower;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("cnot_batch", stream);
-    launchCnotBatch<R>(dState, a, stream);
+    launchCnotBatch<R>(wState(), a, stream);
 }
 
 // batched independent 1q gates: k gates in one full-state pass (k_mtrx_batch).
@@ -719,7 +803,7 @@ void QEngineHIP<R>::Mtrx1qBatch(
         a.k = (int)kp;
         a.maxQPower = maxQPower;
         HipProfScope prof("mtrx_1q_batch_lds", stream);
-        launchMtrx1qBatchLds<R>(dState, a, stream);
+        launchMtrx1qBatchLds<R>(wState(), a, stream);
         i += k;
     }
     size_t i = 0;
@@ -741,7 +825,7 @@ void QEngineHIP<R>::Mtrx1qBatch(
         a.k = (int)k;
         a.maxI = maxQPower >> k;
         HipProfScope prof("mtrx_1q_batch", stream);
-        launchMtrx1qBatch<R>(dState, a, stream);
+        launchMtrx1qBatch<R>(wState(), a, stream);
         i += k;
     }
 }
@@ -750,14 +834,14 @@ template <typename R> void QEngineHIP<R>::XMask(bitCapInt mask)
 {
     if (!mask) return;
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    launchXMask<R>(dState, maxQPower, mask, stream);
+    launchXMask<R>(wState(), maxQPower, mask, stream);
 }
 
 template <typename R> void QEngineHIP<R>::ZMask(bitCapInt mask)
 {
     if (!mask) return;
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    launchParityPhase<R>(dState, maxQPower, mask, cplx<R>(1, 0), cplx<R>(-1, 0), stream);
+    launchParityPhase<R>(wState(), maxQPower, mask, cplx<R>(1, 0), cplx<R>(-1, 0), stream);
 }
 
 template <typename R> void QEngineHIP<R>::PhaseParity(R radians, bitCapInt mask)
@@ -765,7 +849,7 @@ template <typename R> void QEngineHIP<R>::PhaseParity(R radians, bitCapInt mask)
     if (!mask) return;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     launchParityPhase<R>(
-        dState, maxQPower, mask, polar<R>(1, -radians / 2), polar<R>(1, radians / 2), stream);
+        wState(), maxQPower, mask, polar<R>(1, -radians / 2), polar<R>(1, radians / 2), stream);
 }
 
 template <typename R>
@@ -788,7 +872,7 @@ void QEngineHIP<R>::UniformlyControlledSingleBit(
         hipMemcpyHostToDevice, stream));
     QA_HIP_CHECK(
         hipMemcpyAsync(dMtrxs, mtrxs, sizeof(cplx<R>) * 4 * nMtrx, hipMemcpyHostToDevice, stream));
-    launchUniformlyControlled<R>(dState, maxQPower >> 1u, pow2(target), dPowers,
+    launchUniformlyControlled<R>(wState(), maxQPower >> 1u, pow2(target), dPowers,
         (int)controls.size(), dMtrxs, stream);
     QA_HIP_CHECK(hipFreeAsync(dPowers, stream));
     QA_HIP_CHECK(hipFreeAsync(dMtrxs, stream));
@@ -799,7 +883,7 @@ void QEngineHIP<R>::PhaseRamp(R scale, bitLenInt rampStart, bitLenInt rampBits, 
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("phase_ramp", stream);
-    launchPhaseRamp<R>(dState, maxQPower, rampStart, rampBits, condPower, (double)scale, stream);
+    launchPhaseRamp<R>(wState(), maxQPower, rampStart, rampBits, condPower, (double)scale, stream);
 }
 
 template <typename R>
@@ -820,7 +904,7 @@ void QEngineHIP<R>::QftColumnGeneral(bitLenInt target, double scale, bitLenInt r
     a.scale = scale;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("qft_column", stream);
-    launchQftColumnGeneral<R>(dState, maxQPower, pow2(target), a, phase0, pre, stream);
+    launchQftColumnGeneral<R>(wState(), maxQPower, pow2(target), a, phase0, pre, stream);
 }
 
 template <typename R>
@@ -842,7 +926,7 @@ void QEngineHIP<R>::QftColumn2General(bitLenInt targetHi, bitLenInt targetLo, do
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("qft_column2_gen", stream);
     launchQftColumn2General<R>(
-        dState, maxQPower, pow2(targetHi), pow2(targetLo), a, phase0Hi, phase0Lo, pre, stream);
+        wState(), maxQPower, pow2(targetHi), pow2(targetLo), a, phase0Hi, phase0Lo, pre, stream);
 }
 
 template <typename R>
@@ -864,8 +948,13 @@ void QEngineHIP<R>::QftColumnTopRange(double scale, bitLenInt rampStart, bitCapI
     a.scale = scale;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     hipStream_t st = extStream ? (hipStream_t)extStream : stream;
-    launchQftColumnTopRange<R>(dState, maxQPower, a, phase0, pre, (bitCapInt)itLo,
-        (bitCapInt)itHi, (const cplx<R>*)recvPtr, recvIsLow, st);
+    // a pending basis state is filled on the engine's stream: it must have
+    // landed before a kernel on the caller's stream touches the buffer
+    const bool wasPending = basisPending_;
+    cplx<R>* sv = wState();
+    if (wasPending && st != stream) Finish();
+    launchQftColumnTopRange<R>(sv, maxQPower, a, phase0, pre, (bitCapInt)itLo, (bitCapInt)itHi,
+        (const cplx<R>*)recvPtr, recvIsLow, st);
 }
 
 template <typename R>
@@ -888,7 +977,7 @@ void QEngineHIP<R>::PhaseRampGeneral(R scale, bitLenInt rampStart, bitCapInt inP
     a.condPow = condPower;
     a.scale = (double)scale;
     HipProfScope prof("phase_ramp", stream);
-    launchPhaseRampGeneral<R>(dState, maxQPower, a, stream);
+    launchPhaseRampGeneral<R>(wState(), maxQPower, a, stream);
 }
 
 template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length, bool)
@@ -928,23 +1017,35 @@ template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length,
                 // the whole remaining (K-aligned) ladder in ONE LDS pass of
                 // uniform register-orbit groups
                 HipProfScope prof("qft_low_lds", stream);
-                launchQftLowLds<R>(dState, maxQPower, tb, (int)col, +1, false, stream);
+                if (basisPending_) {
+                    // first pass from a pending basis state: write-only
+                    launchQftLowLdsBasis<R>(wStateAll(), maxQPower, tb, (int)col, +1, false,
+                        basisPerm_, basisPhase_, stream);
+                } else if (tileSumsUsable() && maxQPower >= (ONE_BCI << (tb + 11))) {
+                    // final pass: leave per-tile norms for the sampler (used
+                    // once a sampling chunk spans at least one tile)
+                    double* sums = tileSumsBuffer();
+                    launchQftLowLdsSums<R>(wState(), maxQPower, tb, (int)col, sums, stream);
+                    tileSumsValid_ = true;
+                } else {
+                    launchQftLowLds<R>(wState(), maxQPower, tb, (int)col, +1, false, stream);
+                }
                 break;
             }
             if (i != r) {
                 // peel the top r columns so the ladder below is 4-aligned
                 if (r == 3u) {
                     HipProfScope prof("qft_column3", stream);
-                    launchQftColumn3<R>(dState, maxQPower, start, col, pow2(start + col),
+                    launchQftColumn3<R>(wState(), maxQPower, start, col, pow2(start + col),
                         pow2(start + col - 1u), pow2(start + col - 2u), +1, false, stream);
                 } else if (r == 2u) {
                     HipProfScope prof("qft_column2", stream);
-                    launchQftColumn2<R>(dState, maxQPower, start, col, pow2(start + col),
+                    launchQftColumn2<R>(wState(), maxQPower, start, col, pow2(start + col),
                         pow2(start + col - 1u), +1, false, stream);
                 } else {
                     HipProfScope prof("qft_column", stream);
                     launchQftColumn<R>(
-                        dState, maxQPower, start, col, pow2(start + col), +1, false, stream);
+                        wState(), maxQPower, start, col, pow2(start + col), +1, false, stream);
                 }
                 i -= r;
                 continue;
@@ -962,7 +1063,12 @@ template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length,
             const int nc = rem >= 5 ? 6 : rem;
             if (nc >= 2 && (int)i - nc >= 6) {
                 HipProfScope prof("qft_mid_lds", stream);
-                launchQftMidLds<R>(dState, maxQPower, (int)i - nc, nc, +1, false, stream);
+                if (basisPending_) {
+                    launchQftMidLdsBasis<R>(wStateAll(), maxQPower, (int)i - nc, nc, +1, false,
+                        basisPerm_, basisPhase_, stream);
+                } else {
+                    launchQftMidLds<R>(wState(), maxQPower, (int)i - nc, nc, +1, false, stream);
+                }
                 i -= (bitLenInt)nc;
                 continue;
             }
@@ -972,7 +1078,7 @@ template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length,
             HipProfScope prof("qft_column5", stream);
             const bitCapInt tPows[5] = { pow2(start + col - 4u), pow2(start + col - 3u),
                 pow2(start + col - 2u), pow2(start + col - 1u), pow2(start + col) };
-            launchQftColumnK<R>(dState, maxQPower, start, col, 5, tPows, +1, false, stream);
+            launchQftColumnK<R>(wState(), maxQPower, start, col, 5, tPows, +1, false, stream);
             i -= 5u;
             continue;
         }
@@ -980,14 +1086,14 @@ template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length,
             HipProfScope prof("qft_column4", stream);
             const bitCapInt tPows[5] = { pow2(start + col - 3u), pow2(start + col - 2u),
                 pow2(start + col - 1u), pow2(start + col), 0u };
-            launchQftColumnK<R>(dState, maxQPower, start, col, 4, tPows, +1, false, stream);
+            launchQftColumnK<R>(wState(), maxQPower, start, col, 4, tPows, +1, false, stream);
             i -= 4u;
             continue;
         }
         if (fuseMax >= 3 && col >= 2u && maxQPower >= 16u) {
             // three columns per pass (8-amplitude orbits)
             HipProfScope prof("qft_column3", stream);
-            launchQftColumn3<R>(dState, maxQPower, start, col, pow2(start + col),
+            launchQftColumn3<R>(wState(), maxQPower, start, col, pow2(start + col),
                 pow2(start + col - 1u), pow2(start + col - 2u), +1, false, stream);
             i -= 3u;
             continue;
@@ -995,7 +1101,7 @@ template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length,
         if (fuseMax >= 2 && col >= 1u && maxQPower >= 8u) {
             // two columns per pass
             HipProfScope prof("qft_column2", stream);
-            launchQftColumn2<R>(dState, maxQPower, start, col, pow2(start + col),
+            launchQftColumn2<R>(wState(), maxQPower, start, col, pow2(start + col),
                 pow2(start + col - 1u), +1, false, stream);
             i -= 2u;
             continue;
@@ -1005,7 +1111,7 @@ template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length,
             break;
         }
         HipProfScope prof("qft_column", stream);
-        launchQftColumn<R>(dState, maxQPower, start, col, pow2(start + col), +1, false, stream);
+        launchQftColumn<R>(wState(), maxQPower, start, col, pow2(start + col), +1, false, stream);
         --i;
     }
 }
@@ -1039,7 +1145,12 @@ template <typename R> void QEngineHIP<R>::IQFT(bitLenInt start, bitLenInt length
         const bitLenInt L = (std::min<bitLenInt>(length, (bitLenInt)tb) / AK) * AK;
         if (L >= AK) {
             HipProfScope prof("qft_low_lds", stream);
-            launchQftLowLds<R>(dState, maxQPower, tb, (int)L - 1, -1, true, stream);
+            if (basisPending_) {
+                launchQftLowLdsBasis<R>(wStateAll(), maxQPower, tb, (int)L - 1, -1, true,
+                    basisPerm_, basisPhase_, stream);
+            } else {
+                launchQftLowLds<R>(wState(), maxQPower, tb, (int)L - 1, -1, true, stream);
+            }
             i = L;
         }
     }
@@ -1050,7 +1161,12 @@ template <typename R> void QEngineHIP<R>::IQFT(bitLenInt start, bitLenInt length
             const int nc = rem >= 6 ? 6 : (rem == 5 ? 4 : rem);
             if (nc >= 2) {
                 HipProfScope prof("qft_mid_lds", stream);
-                launchQftMidLds<R>(dState, maxQPower, (int)i, nc, -1, true, stream);
+                if (basisPending_) {
+                    launchQftMidLdsBasis<R>(wStateAll(), maxQPower, (int)i, nc, -1, true,
+                        basisPerm_, basisPhase_, stream);
+                } else {
+                    launchQftMidLds<R>(wState(), maxQPower, (int)i, nc, -1, true, stream);
+                }
                 i += (bitLenInt)nc;
                 continue;
             }
@@ -1060,7 +1176,7 @@ template <typename R> void QEngineHIP<R>::IQFT(bitLenInt start, bitLenInt length
             const bitCapInt tPows[5] = { pow2(start + i), pow2(start + i + 1u),
                 pow2(start + i + 2u), pow2(start + i + 3u), pow2(start + i + 4u) };
             launchQftColumnK<R>(
-                dState, maxQPower, start, (bitLenInt)(i + 4u), 5, tPows, -1, true, stream);
+                wState(), maxQPower, start, (bitLenInt)(i + 4u), 5, tPows, -1, true, stream);
             i += 5u;
             continue;
         }
@@ -1069,7 +1185,7 @@ template <typename R> void QEngineHIP<R>::IQFT(bitLenInt start, bitLenInt length
             const bitCapInt tPows[5] = { pow2(start + i), pow2(start + i + 1u),
                 pow2(start + i + 2u), pow2(start + i + 3u), 0u };
             launchQftColumnK<R>(
-                dState, maxQPower, start, (bitLenInt)(i + 3u), 4, tPows, -1, true, stream);
+                wState(), maxQPower, start, (bitLenInt)(i + 3u), 4, tPows, -1, true, stream);
             i += 4u;
             continue;
         }
@@ -1077,14 +1193,14 @@ template <typename R> void QEngineHIP<R>::IQFT(bitLenInt start, bitLenInt length
             // triple (lo=i, mid=i+1, hi=i+2): exact adjoint of the forward
             // triple (a lo column of 0 degenerates to the plain H inside)
             HipProfScope prof("qft_column3", stream);
-            launchQftColumn3<R>(dState, maxQPower, start, (bitLenInt)(i + 2u),
+            launchQftColumn3<R>(wState(), maxQPower, start, (bitLenInt)(i + 2u),
                 pow2(start + i + 2u), pow2(start + i + 1u), pow2(start + i), -1, true, stream);
             i += 3u;
             continue;
         }
         if (fuseMax >= 2 && (i + 1u) < length && maxQPower >= 8u) {
             HipProfScope prof("qft_column2", stream);
-            launchQftColumn2<R>(dState, maxQPower, start, (bitLenInt)(i + 1u),
+            launchQftColumn2<R>(wState(), maxQPower, start, (bitLenInt)(i + 1u),
                 pow2(start + i + 1u), pow2(start + i), -1, true, stream);
             i += 2u;
             continue;
@@ -1095,7 +1211,7 @@ template <typename R> void QEngineHIP<R>::IQFT(bitLenInt start, bitLenInt length
             continue;
         }
         HipProfScope prof("qft_column", stream);
-        launchQftColumn<R>(dState, maxQPower, start, i, pow2(start + i), -1, true, stream);
+        launchQftColumn<R>(wState(), maxQPower, start, i, pow2(start + i), -1, true, stream);
         ++i;
     }
 }
@@ -1106,7 +1222,7 @@ template <typename R> double QEngineHIP<R>::reduceSum(int op, const ReduceArgs& 
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("reduce", stream);
-    const int grid = launchReduce<R>(dState, a, op, dPartials, stream);
+    const int grid = launchReduce<R>(rState(), a, op, dPartials, stream);
     QA_HIP_CHECK(hipMemcpyAsync(
         hPartials.data(), dPartials, grid * sizeof(double), hipMemcpyDeviceToHost, stream));
     Finish();
@@ -1118,7 +1234,7 @@ template <typename R> double QEngineHIP<R>::reduceSum(int op, const ReduceArgs& 
 template <typename R> std::pair<double, bitCapInt> QEngineHIP<R>::argMax()
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    const int grid = launchArgMax<R>(dState, maxQPower, dPartials, dIdx, stream);
+    const int grid = launchArgMax<R>(rState(), maxQPower, dPartials, dIdx, stream);
     std::vector<bitCapInt> hIdx(grid);
     QA_HIP_CHECK(hipMemcpyAsync(
         hPartials.data(), dPartials, grid * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1175,7 +1291,7 @@ template <typename R> bool QEngineHIP<R>::ForceMParity(bitCapInt mask, bool resu
     if (prob <= 0) throw QrackError("ForceMParity: impossible outcome");
     const R nrm = (R)1 / std::sqrt(prob);
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    launchApplyParity<R>(dState, maxQPower, mask, result, cplx<R>(nrm, 0), stream);
+    launchApplyParity<R>(wState(), maxQPower, mask, result, cplx<R>(nrm, 0), stream);
     runningNorm = (R)1;
     return result;
 }
@@ -1183,7 +1299,7 @@ template <typename R> bool QEngineHIP<R>::ForceMParity(bitCapInt mask, bool resu
 template <typename R> void QEngineHIP<R>::ApplyM(bitCapInt regMask, bitCapInt result, cplx<R> nrm)
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    launchApplyM<R>(dState, maxQPower, regMask, result, nrm, stream);
+    launchApplyM<R>(wState(), maxQPower, regMask, result, nrm, stream);
     runningNorm = (R)1;
 }
 
@@ -1234,7 +1350,14 @@ template <typename R> std::vector<double> QEngineHIP<R>::chunkSums(bitCapInt& ch
     const bitCapInt chunkLen = maxQPower / nChunks;
     chunkLenOut = chunkLen;
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    launchChunkSums<R>(dState, nChunks, chunkLen, dPartials, stream);
+    const int tb = qaLdsTileBits<R>();
+    if (tileSumsValid_ && tileSumsUsable() && dTileSums_ && chunkLen >= (ONE_BCI << tb)) {
+        // the last QFT pass left per-tile norms of exactly this state: add
+        // them per chunk instead of re-reading the whole state
+        launchTileChunkSums(dTileSums_, nChunks, chunkLen >> tb, dPartials, stream);
+    } else {
+        launchChunkSums<R>(rState(), nChunks, chunkLen, dPartials, stream);
+    }
     std::vector<double> sums(nChunks);
     QA_HIP_CHECK(hipMemcpyAsync(
         sums.data(), dPartials, nChunks * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1329,7 +1452,7 @@ template <typename R> void QEngineHIP<R>::NormalizeState(R nrm, R norm_thresh, R
     if (norm_thresh < 0) norm_thresh = amplitudeFloor;
     const cplx<R> factor = polar<R>((R)(1.0 / std::sqrt((double)nrm)), phaseArg);
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    launchNormalize<R>(dState, maxQPower, factor, norm_thresh * nrm, stream);
+    launchNormalize<R>(wState(), maxQPower, factor, norm_thresh * nrm, stream);
     runningNorm = (R)1;
 }
 
@@ -1338,11 +1461,11 @@ template <typename R> double QEngineHIP<R>::SumSqrDiff(QInterfacePtr<R> other)
     if (other->GetQubitCount() != qubitCount) return 2.0;
     QEngineHIP<R>* o = dynamic_cast<QEngineHIP<R>*>(other.get());
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    cplx<R>* otherBuf = nullptr;
+    const cplx<R>* otherBuf = nullptr;
     cplx<R>* tmp = nullptr;
     if (o && o->deviceId == deviceId) {
+        otherBuf = o->rState();
         o->Finish();
-        otherBuf = o->dState;
     } else {
         std::vector<cplx<R>> host(maxQPower);
         other->GetQuantumState(host.data());
@@ -1352,7 +1475,7 @@ template <typename R> double QEngineHIP<R>::SumSqrDiff(QInterfacePtr<R> other)
         otherBuf = tmp;
     }
     const int grid = launchInner<R>(
-        dState, otherBuf, maxQPower, dPartials, dPartials + QA_REDUCE_MAX_BLOCKS, stream);
+        rState(), otherBuf, maxQPower, dPartials, dPartials + QA_REDUCE_MAX_BLOCKS, stream);
     QA_HIP_CHECK(hipMemcpyAsync(
         hPartials.data(), dPartials, grid * sizeof(double), hipMemcpyDeviceToHost, stream));
     QA_HIP_CHECK(hipMemcpyAsync(hPartials.data() + QA_REDUCE_MAX_BLOCKS,
@@ -1376,11 +1499,11 @@ template <typename R> bitLenInt QEngineHIP<R>::Compose(QInterfacePtr<R> toCopy, 
     const bitCapInt nMaxQPower = maxQPower << oQubits;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     QEngineHIP<R>* o = dynamic_cast<QEngineHIP<R>*>(toCopy.get());
-    cplx<R>* otherBuf = nullptr;
+    const cplx<R>* otherBuf = nullptr;
     cplx<R>* tmp = nullptr;
     if (o && o->deviceId == deviceId) {
+        otherBuf = o->rState();
         o->Finish();
-        otherBuf = o->dState;
     } else {
         std::vector<cplx<R>> host(toCopy->GetMaxQPower());
         toCopy->GetQuantumState(host.data());
@@ -1390,7 +1513,7 @@ template <typename R> bitLenInt QEngineHIP<R>::Compose(QInterfacePtr<R> toCopy, 
         otherBuf = tmp;
     }
     cplx<R>* nBuf = allocDev(nMaxQPower);
-    launchCompose<R>(dState, otherBuf, nBuf, nMaxQPower, start, oQubits, stream);
+    launchCompose<R>(rState(), otherBuf, nBuf, nMaxQPower, start, oQubits, stream);
     Finish();
     if (tmp) freeDev(tmp, toCopy->GetMaxQPower());
     resizeState(nMaxQPower, nBuf);
@@ -1406,7 +1529,7 @@ template <typename R> std::vector<double> QEngineHIP<R>::partProbs(bitLenInt sta
     double* dProbs = nullptr;
     QA_HIP_CHECK(hipMallocAsync(&dProbs, partPower * sizeof(double), stream));
     QA_HIP_CHECK(hipMemsetAsync(dProbs, 0, partPower * sizeof(double), stream));
-    launchPartProbs<R>(dState, maxQPower, start, length, dProbs, stream);
+    launchPartProbs<R>(rState(), maxQPower, start, length, dProbs, stream);
     std::vector<double> probs(partPower);
     QA_HIP_CHECK(hipMemcpyAsync(
         probs.data(), dProbs, partPower * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1451,12 +1574,12 @@ template <typename R> void QEngineHIP<R>::Decompose(bitLenInt start, QInterfaceP
     cplx<R>* dDest = nullptr;
     bool destLocal = od && od->deviceId == deviceId;
     if (destLocal) {
+        dDest = od->wState();
         od->Finish();
-        dDest = od->dState;
     } else {
         QA_HIP_CHECK(hipMallocAsync(&dDest, partPower * sizeof(cplx<R>), stream));
     }
-    launchGatherPart<R>(dState, dDest, partPower, start, len, rStar, cplx<R>((R)rNorm, 0), stream);
+    launchGatherPart<R>(rState(), dDest, partPower, start, len, rStar, cplx<R>((R)rNorm, 0), stream);
 
     // remainder amplitudes, with the double-counted-phase correction folded in
     cplx<R>* nBuf = allocDev(remPower);
@@ -1472,7 +1595,7 @@ template <typename R> void QEngineHIP<R>::Decompose(bitLenInt start, QInterfaceP
     } else {
         corrScale = cplx<R>((R)pNorm, 0);
     }
-    launchDisposeSlice<R>(dState, nBuf, remPower, start, len, pStar, corrScale, stream);
+    launchDisposeSlice<R>(rState(), nBuf, remPower, start, len, pStar, corrScale, stream);
     Finish();
 
     if (destLocal) {
@@ -1502,7 +1625,7 @@ template <typename R> void QEngineHIP<R>::Dispose(bitLenInt start, bitLenInt len
     const bitCapInt remPower = maxQPower >> length;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     cplx<R>* nBuf = allocDev(remPower);
-    launchDisposeSlice<R>(dState, nBuf, remPower, start, length, pStar, cplx<R>((R)scale, 0), stream);
+    launchDisposeSlice<R>(rState(), nBuf, remPower, start, length, pStar, cplx<R>((R)scale, 0), stream);
     Finish();
     resizeState(remPower, nBuf);
     this->SetQubitCount(qubitCount - length);
@@ -1515,7 +1638,7 @@ void QEngineHIP<R>::Dispose(bitLenInt start, bitLenInt length, bitCapInt dispose
     const bitCapInt remPower = maxQPower >> length;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     cplx<R>* nBuf = allocDev(remPower);
-    launchDisposeSlice<R>(dState, nBuf, remPower, start, length, disposedPerm, cplx<R>(1, 0), stream);
+    launchDisposeSlice<R>(rState(), nBuf, remPower, start, length, disposedPerm, cplx<R>(1, 0), stream);
     Finish();
     resizeState(remPower, nBuf);
     this->SetQubitCount(qubitCount - length);
@@ -1529,7 +1652,7 @@ template <typename R> bitLenInt QEngineHIP<R>::Allocate(bitLenInt start, bitLenI
     const bitCapInt nMaxQPower = maxQPower << length;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     cplx<R>* nBuf = allocDev(nMaxQPower);
-    launchAllocateExpand<R>(dState, nBuf, nMaxQPower, start, length, stream);
+    launchAllocateExpand<R>(rState(), nBuf, nMaxQPower, start, length, stream);
     Finish();
     resizeState(nMaxQPower, nBuf);
     this->SetQubitCount(qubitCount + length);
@@ -1540,10 +1663,11 @@ template <typename R> QInterfacePtr<R> QEngineHIP<R>::Clone()
 {
     auto clone = std::make_shared<QEngineHIP<R>>(
         qubitCount, 0u, this->rand_generator, doNormalize, amplitudeFloor, deviceId);
+    const cplx<R>* srcBuf = rState();
     Finish();
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    QA_HIP_CHECK(hipMemcpyAsync(
-        clone->dState, dState, sizeof(cplx<R>) * maxQPower, hipMemcpyDeviceToDevice, clone->stream));
+    QA_HIP_CHECK(hipMemcpyAsync(clone->wStateAll(), srcBuf, sizeof(cplx<R>) * maxQPower,
+        hipMemcpyDeviceToDevice, clone->stream));
     clone->Finish();
     clone->runningNorm = runningNorm;
     return clone;
@@ -1558,11 +1682,11 @@ template <typename R> void QEngineHIP<R>::permuteOp(PermArgs& a, bool partialSpa
     ensureScratch();
     if (copyFirst) {
         QA_HIP_CHECK(hipMemcpyAsync(
-            dScratch, dState, sizeof(cplx<R>) * maxQPower, hipMemcpyDeviceToDevice, stream));
+            dScratch, rState(), sizeof(cplx<R>) * maxQPower, hipMemcpyDeviceToDevice, stream));
     } else if (partialSpace) {
         QA_HIP_CHECK(hipMemsetAsync(dScratch, 0, sizeof(cplx<R>) * maxQPower, stream));
     }
-    launchPermute<R>(dState, dScratch, a, stream);
+    launchPermute<R>(rState(), dScratch, a, stream);
     Finish();
     swapScratch();
 }
@@ -2026,7 +2150,7 @@ void QEngineHIP<R>::PhaseFlipIfLess(bitCapInt greaterPerm, bitLenInt start, bitL
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
     launchPhaseFlipIfLess<R>(
-        dState, maxQPower, greaterPerm, start, pow2Mask(length) << start, 0u, stream);
+        wState(), maxQPower, greaterPerm, start, pow2Mask(length) << start, 0u, stream);
 }
 
 template <typename R>
@@ -2035,7 +2159,7 @@ void QEngineHIP<R>::CPhaseFlipIfLess(
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));
     launchPhaseFlipIfLess<R>(
-        dState, maxQPower, greaterPerm, start, pow2Mask(length) << start, pow2(flagIndex), stream);
+        wState(), maxQPower, greaterPerm, start, pow2Mask(length) << start, pow2(flagIndex), stream);
 }
 
 size_t HipActiveAllocImpl(int device)

@@ -84,8 +84,7 @@ protected:
 
     int deviceId;
     hipStream_t stream;
-    cplx<R>* dState = nullptr;
-    cplx<R>* dScratch = nullptr; // same size as dState, lazily allocated
+    cplx<R>* dScratch = nullptr; // same size as the state buffer, lazily allocated
     double* dPartials = nullptr; // reduce partials (QA-reduce grid max + argmax idx)
     bitCapInt* dIdx = nullptr;
     std::vector<double> hPartials;
@@ -98,8 +97,10 @@ public:
 
     int DeviceId() const { return deviceId; }
     hipStream_t Stream() const { return stream; }
-    cplx<R>* DeviceBuffer() { return dState; }
-    uintptr_t DevicePtr() { return (uintptr_t)dState; }
+    // raw views for code the engine cannot see (dlpack, the dist pager):
+    // they count as writes, and tile sums are never trusted again afterwards
+    cplx<R>* DeviceBuffer() { return externState(); }
+    uintptr_t DevicePtr() { return (uintptr_t)externState(); }
 
     void Finish() override { QA_HIP_CHECK(hipStreamSynchronize(stream)); }
     bool isFinished() override { return hipStreamQuery(stream) == hipSuccess; }
@@ -254,6 +255,62 @@ protected:
     void permuteOp(PermArgs& a, bool partialSpace, bool copyFirst);
     GateArgs<R> makeGateArgs(bitCapInt offset1, bitCapInt offset2, const cplx<R>* mtrx,
         const std::vector<bitCapInt>& qPowersSorted);
+
+    // ---- state buffer access ----
+    // The buffer is reached ONLY through these accessors, so no site can
+    // see a stale buffer or leave stale tile sums behind:
+    //  - rState(): read access; materialises a pending basis state and
+    //    keeps the tile sums
+    //  - wState(): write access; materialises and drops the tile sums
+    //  - wStateAll(): the caller overwrites EVERY amplitude; drops a pending
+    //    basis state without materialising it, and drops the tile sums
+    const cplx<R>* rState()
+    {
+        materialize();
+        return dState_;
+    }
+    cplx<R>* wState()
+    {
+        materialize();
+        tileSumsValid_ = false;
+        return dState_;
+    }
+    cplx<R>* wStateAll()
+    {
+        basisPending_ = false;
+        tileSumsValid_ = false;
+        return dState_;
+    }
+    cplx<R>* externState()
+    {
+        // the caller works on streams of its own: a fill queued here must
+        // have landed before the pointer is handed out
+        const bool wasPending = basisPending_;
+        externView_ = true;
+        cplx<R>* p = wState();
+        if (wasPending) Finish();
+        return p;
+    }
+
+private:
+    void materialize(); // pending basis state -> real buffer (memset + one amplitude)
+    void setStateBuffer(cplx<R>* buf); // adopt a new buffer (contents defined by the caller)
+    double* tileSumsBuffer();          // lazily allocated, maxQPower >> tile bits doubles
+    void releaseTileSums();
+    bool tileSumsUsable() const;       // switch on, no external view taken
+
+    cplx<R>* dState_ = nullptr;
+    // lazy basis state: the state is basisPhase_·|basisPerm_> and the
+    // buffer contents are undefined until materialize() or a synthesised
+    // first QFT pass defines them
+    bool basisPending_ = false;
+    bitCapInt basisPerm_ = 0;
+    cplx<R> basisPhase_ = cplx<R>((R)1, (R)0);
+    // per-tile norms left by the last forward low-ladder QFT pass
+    double* dTileSums_ = nullptr;
+    bitCapInt tileSumsLen_ = 0;
+    bool tileSumsValid_ = false;
+    bool externView_ = false; // sticky: a raw pointer escaped this engine
 };
 
 } // namespace qrack_amd
