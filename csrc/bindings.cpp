@@ -409,6 +409,25 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
                 for (int p : paulis) ps.push_back((Pauli)p);
                 return q.VariancePauliAll(bits, ps);
             })
+        .def("expectation_pauli_sum",
+            [](QI& q,
+                std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms) {
+                std::vector<PauliTerm> ts;
+                ts.reserve(terms.size());
+                for (auto& t : terms) {
+                    PauliTerm pt;
+                    pt.coeff = std::get<0>(t);
+                    pt.bits = std::get<1>(t);
+                    for (int p : std::get<2>(t)) {
+                        if (p < 0 || p > 3) throw QrackError("expectation_pauli_sum: bad Pauli code");
+                        pt.paulis.push_back((Pauli)p);
+                    }
+                    ts.push_back(std::move(pt));
+                }
+                return q.ExpectationPauliSum(ts);
+            },
+            py::arg("terms"),
+            "sum_t coeff_t <P_t> for terms (coeff, [qubits], [paulis]); Pauli codes 0=I 1=X 2=Z 3=Y")
         .def("prob_bits_all",
             [](QI& q, std::vector<bitLenInt> bits) {
                 py::array_t<double> out((py::ssize_t)pow2((bitLenInt)bits.size()));
@@ -837,6 +856,8 @@ PYBIND11_MODULE(_qrack, m)
         return d;
     });
     m.def("profile_reset", []() { HipProfiler::Reset(); });
+    // terms of one X/Y mask that the HIP engine serves per launch
+    m.attr("PAULI_MAX_TERMS") = (int)QA_PAULI_MAX_TERMS;
 #else
     m.def("profile_report", []() { return py::dict(); });
     m.def("profile_reset", []() {});

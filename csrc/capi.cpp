@@ -535,6 +535,27 @@ double qrack_joint_ensemble_probability(
     });
 }
 
+double qrack_expectation_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis)
+{
+    return guardedD(sid, [&](SimSlot& s) -> double {
+        std::vector<PauliTerm> terms(nTerms);
+        uint64_t at = 0;
+        for (uint64_t t = 0; t < nTerms; ++t) {
+            terms[t].coeff = coeffs[t];
+            for (uint64_t i = 0; i < termLens[t]; ++i, ++at) {
+                if (paulis[at] < 0 || paulis[at] > 3)
+                    throw QrackError("qrack_expectation_pauli_sum: bad Pauli code");
+                terms[t].bits.push_back((bitLenInt)qs[at]);
+                terms[t].paulis.push_back((Pauli)paulis[at]);
+            }
+        }
+        double e = 0;
+        FOR_SIM(s, e = q.ExpectationPauliSum(terms));
+        return e;
+    });
+}
+
 void qrack_qft(quid sid, uint64_t start, uint64_t length)
 {
     guarded(sid, [&](SimSlot& s) { FOR_SIM(s, q.QFT((bitLenInt)start, (bitLenInt)length)); });

@@ -3166,6 +3166,164 @@ void launchPartProbs(const cplx<R>* sv, bitCapInt maxQPower, bitLenInt start, bi
     }
 }
 
+// ---- Pauli-sum expectation -------------------------------------------------------
+//
+// <psi|P|psi> with P|i> = i^ny (-1)^popcount(i&z) |i^x>. For x != 0 the pair
+// (i, i^x) contributes 2 Re(w(i) conj(psi[i^x]) psi[i]) with
+// w(i) = sum_t c_t i^ny_t (-1)^popcount(i&z_t), so only the half-space with
+// the top bit of x clear is walked: every amplitude is loaded once and nothing
+// is stored. fp32 streams float4 (two amplitudes): i is even, i+1 shares the
+// vector, and the partner vector sits at i ^ (x & ~1) — with bit 0 of x set
+// its halves are swapped in registers. x == 1 pairs the two halves of one
+// vector. fp64 amplitudes are 16 B each already.
+
+// block sum in a fixed order: wave shuffle -> LDS -> one double
+__device__ __forceinline__ void blockSumStore(double s, double* dst)
+{
+    s = waveReduceSum(s);
+    __shared__ double waveSums[QA_BLOCK / 64];
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    if (lane == 0) waveSums[wid] = s;
+    __syncthreads();
+    if (wid == 0) {
+        double t = (lane < QA_BLOCK / 64) ? waveSums[lane] : 0.0;
+        t = waveReduceSum(t);
+        if (lane == 0) *dst = t;
+    }
+}
+
+// weights of index i (even when TWO) and, when TWO, of i + 1
+template <bool TWO>
+__device__ __forceinline__ void pauliWeights(const PauliArgs& a, int first, int last, bitCapInt i,
+    double& w0, double& w1)
+{
+    w0 = 0;
+    w1 = 0;
+    for (int t = first; t < last; ++t) {
+        const bitCapInt z = a.z[t];
+        const double c = a.w[t];
+        const unsigned p0 = __popcll(i & z) & 1u;
+        w0 += p0 ? -c : c;
+        if (TWO) {
+            const unsigned p1 = p0 ^ (unsigned)(z & 1u);
+            w1 += p1 ? -c : c;
+        }
+    }
+}
+
+// 2 Re((wr + i wi) conj(b) a)
+template <typename R>
+__device__ __forceinline__ double pauliPair(R are, R aim, R bre, R bim, double wr, double wi)
+{
+    const R pr = bre * are + bim * aim;
+    const R pi = bre * aim - bim * are;
+    return 2.0 * (wr * (double)pr - wi * (double)pi);
+}
+
+// MODE 0: one pair per item (fp64); 1: two pairs per item (fp32, x != 1);
+// 2: fp32, x == 1
+template <typename R, int MODE>
+__global__ void k_pauli_group(const cplx<R>* sv, PauliArgs a, bitCapInt nItems, bitCapInt topPow,
+    double* partials)
+{
+    double s = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        double wr0, wr1, wi0, wi1;
+        if constexpr (MODE == 0) {
+            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
+            const double2 A = reinterpret_cast<const double2*>(sv)[i];
+            const double2 B = reinterpret_cast<const double2*>(sv)[i ^ a.x];
+            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            s += pauliPair<double>(A.x, A.y, B.x, B.y, wr0, wi0);
+        } else if constexpr (MODE == 1) {
+            const bitCapInt j = v << 1u;
+            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
+            const float4 A = reinterpret_cast<const float4*>(sv)[i >> 1u];
+            float4 B = reinterpret_cast<const float4*>(sv)[(i ^ a.x) >> 1u];
+            if (a.x & 1u) B = make_float4(B.z, B.w, B.x, B.y);
+            pauliWeights<true>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<true>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            s += pauliPair<float>(A.x, A.y, B.x, B.y, wr0, wi0);
+            s += pauliPair<float>(A.z, A.w, B.z, B.w, wr1, wi1);
+        } else {
+            const bitCapInt i = v << 1u;
+            const float4 A = reinterpret_cast<const float4*>(sv)[v];
+            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            s += pauliPair<float>(A.x, A.y, A.z, A.w, wr0, wi0);
+        }
+    }
+    blockSumStore(s, partials + blockIdx.x);
+}
+
+// x == 0: sum_i |psi[i]|^2 sum_t c_t (-1)^popcount(i&z_t)
+template <typename R> __global__ void k_pauli_diag(const cplx<R>* sv, PauliArgs a, bitCapInt nItems, double* partials)
+{
+    double s = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        double w0, w1;
+        if constexpr (sizeof(R) == 4) {
+            const float4 A = reinterpret_cast<const float4*>(sv)[v];
+            pauliWeights<true>(a, 0, a.nTerms, v << 1u, w0, w1);
+            s += w0 * (double)(A.x * A.x + A.y * A.y) + w1 * (double)(A.z * A.z + A.w * A.w);
+        } else {
+            const double2 A = reinterpret_cast<const double2*>(sv)[v];
+            pauliWeights<false>(a, 0, a.nTerms, v, w0, w1);
+            s += w0 * (A.x * A.x + A.y * A.y);
+        }
+    }
+    blockSumStore(s, partials + blockIdx.x);
+}
+
+// stage 2: fold one launch's block partials, in a fixed order, into one double
+__global__ void k_pauli_finish(const double* partials, int n, double* result)
+{
+    double s = 0;
+    for (int k = threadIdx.x; k < n; k += QA_BLOCK) s += partials[k];
+    blockSumStore(s, result);
+}
+
+template <typename R>
+void launchPauliGroup(const cplx<R>* sv, const PauliArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream)
+{
+    // an item is one 16-byte load per stream: two amplitudes in fp32, one in fp64
+    bitCapInt nItems;
+    int grid;
+    if (!a.x) {
+        nItems = (sizeof(R) == 4) ? (a.nAmps >> 1u) : a.nAmps;
+        grid = gridForReduce(nItems);
+        hipLaunchKernelGGL((k_pauli_diag<R>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv, a, nItems,
+            partialsDev);
+    } else {
+        const bitCapInt topPow = ONE_BCI << (63 - __builtin_clzll(a.x));
+        if constexpr (sizeof(R) == 4) {
+            if (a.x == 1u) {
+                nItems = a.nAmps >> 1u;
+                grid = gridForReduce(nItems);
+                hipLaunchKernelGGL((k_pauli_group<R, 2>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv,
+                    a, nItems, topPow, partialsDev);
+            } else {
+                nItems = a.nAmps >> 2u;
+                grid = gridForReduce(nItems);
+                hipLaunchKernelGGL((k_pauli_group<R, 1>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv,
+                    a, nItems, topPow, partialsDev);
+            }
+        } else {
+            nItems = a.nAmps >> 1u;
+            grid = gridForReduce(nItems);
+            hipLaunchKernelGGL((k_pauli_group<R, 0>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv, a,
+                nItems, topPow, partialsDev);
+        }
+    }
+    hipLaunchKernelGGL(
+        k_pauli_finish, dim3(1), dim3(QA_BLOCK), 0, stream, partialsDev, grid, resultDev);
+}
+
 // ---- explicit instantiations ---------------------------------------------------
 
 #define QA_INSTANTIATE(R)                                                                           \
@@ -3176,6 +3334,7 @@ void launchPartProbs(const cplx<R>* sv, bitCapInt maxQPower, bitLenInt start, bi
     template void launchParityPhase<R>(cplx<R>*, bitCapInt, bitCapInt, cplx<R>, cplx<R>, hipStream_t); \
     template int launchReduce<R>(const cplx<R>*, const ReduceArgs&, int, double*, hipStream_t);     \
     template int launchArgMax<R>(const cplx<R>*, bitCapInt, double*, bitCapInt*, hipStream_t);      \
+    template void launchPauliGroup<R>(const cplx<R>*, const PauliArgs&, double*, double*, hipStream_t); \
     template void launchNormalize<R>(cplx<R>*, bitCapInt, cplx<R>, R, hipStream_t);                 \
     template void launchApplyM<R>(cplx<R>*, bitCapInt, bitCapInt, bitCapInt, cplx<R>, hipStream_t); \
     template void launchApplyParity<R>(cplx<R>*, bitCapInt, bitCapInt, bool, cplx<R>, hipStream_t); \

@@ -94,7 +94,30 @@ struct ReduceArgs {
     int nBits;
 };
 
+// One launch of the Pauli-sum pass: up to QA_PAULI_MAX_TERMS strings that
+// share the flip mask x, each with its sign mask z and weight coeff * i^ny.
+// Terms [0, nRe) carry real weights, [nRe, nTerms) imaginary ones. Like
+// ReduceArgs the table rides in the kernarg segment (~530 B), so the per-term
+// loop reads it with scalar loads and no staging buffer exists.
+constexpr int QA_PAULI_MAX_TERMS = 32;
+
+struct PauliArgs {
+    bitCapInt x;     // X/Y mask; 0 selects the diagonal kernel
+    bitCapInt nAmps; // 2^qubits
+    int nRe;
+    int nTerms;
+    bitCapInt z[QA_PAULI_MAX_TERMS];
+    double w[QA_PAULI_MAX_TERMS];
+};
+
 // ---- launches (all asynchronous on `stream`) -------------------------------
+
+// sum_t w_t <psi|P_t|psi> for one group: stage 1 leaves per-block partials in
+// partialsDev (QA_REDUCE_MAX_BLOCKS doubles), stage 2 folds them in a fixed
+// order into *resultDev. Reads sv only.
+template <typename R>
+void launchPauliGroup(const cplx<R>* sv, const PauliArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream);
 
 template <typename R>
 void launchApply2x2(cplx<R>* sv, const GateArgs<R>& a, hipStream_t stream);

@@ -1231,6 +1231,102 @@ template <typename R> double QEngineHIP<R>::reduceSum(int op, const ReduceArgs& 
     return s;
 }
 
+// ---- Pauli strings and sums -------------------------------------------------
+
+template <typename R> double QEngineHIP<R>::pauliGroupsSum(const std::vector<PauliGroup>& groups)
+{
+    // One launch per (group, chunk of QA_PAULI_MAX_TERMS terms). Each launch
+    // folds its block partials (first half of dPartials) into one double in
+    // the second half; the whole call's results come back in one copy.
+    std::vector<PauliArgs> launches;
+    for (const PauliGroup& g : groups) {
+        size_t r = 0, m = 0;
+        while (r < g.re.size() || m < g.im.size()) {
+            PauliArgs a{};
+            a.x = g.x;
+            a.nAmps = maxQPower;
+            while (a.nTerms < QA_PAULI_MAX_TERMS && r < g.re.size()) {
+                a.z[a.nTerms] = g.re[r].z;
+                a.w[a.nTerms++] = g.re[r++].w;
+            }
+            a.nRe = a.nTerms;
+            while (a.nTerms < QA_PAULI_MAX_TERMS && m < g.im.size()) {
+                a.z[a.nTerms] = g.im[m].z;
+                a.w[a.nTerms++] = g.im[m++].w;
+            }
+            launches.push_back(a);
+        }
+    }
+    if (launches.empty()) return 0.0;
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    HipProfScope prof("pauli", stream);
+    const cplx<R>* sv = rState();
+    double* dResults = dPartials + QA_REDUCE_MAX_BLOCKS;
+    double* hResults = hPartials.data() + QA_REDUCE_MAX_BLOCKS;
+    double total = 0;
+    for (size_t base = 0; base < launches.size(); base += QA_REDUCE_MAX_BLOCKS) {
+        const size_t n = std::min<size_t>(QA_REDUCE_MAX_BLOCKS, launches.size() - base);
+        for (size_t k = 0; k < n; ++k) {
+            launchPauliGroup<R>(sv, launches[base + k], dPartials, dResults + k, stream);
+        }
+        QA_HIP_CHECK(hipMemcpyAsync(
+            hResults, dResults, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+        Finish();
+        for (size_t k = 0; k < n; ++k) total += hResults[k];
+    }
+    return total;
+}
+
+template <typename R>
+bool QEngineHIP<R>::pauliStringNative(const std::vector<bitLenInt>& bits,
+    const std::vector<Pauli>& paulis, const char* what, double& value)
+{
+    if (bits.size() != paulis.size()) throw QrackError(std::string(what) + ": size mismatch");
+    bitCapInt x, z;
+    // a repeated or out-of-range qubit keeps the generic lowering's behaviour
+    if (!pauliStringMasks(bits, paulis, qubitCount, x, z)) return false;
+    if (!x) {
+        value = 1.0 - 2.0 * (double)ProbParity(z);
+        return true;
+    }
+    value = pauliGroupsSum({ pauliStringGroup(x, z, 1.0) });
+    return true;
+}
+
+template <typename R>
+double QEngineHIP<R>::PauliExpectation(
+    const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis)
+{
+    double e;
+    if (pauliStringNative(bits, paulis, "PauliExpectation", e)) return e;
+    return QInterface<R>::PauliExpectation(bits, paulis);
+}
+
+template <typename R>
+double QEngineHIP<R>::ExpectationPauliAll(
+    const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis)
+{
+    double e;
+    if (pauliStringNative(bits, paulis, "ExpectationPauliAll", e)) return e;
+    return QInterface<R>::ExpectationPauliAll(bits, paulis);
+}
+
+template <typename R>
+double QEngineHIP<R>::VariancePauliAll(
+    const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis)
+{
+    double e;
+    // the product observable squares to the identity
+    if (pauliStringNative(bits, paulis, "VariancePauliAll", e)) return 1.0 - e * e;
+    return QInterface<R>::VariancePauliAll(bits, paulis);
+}
+
+template <typename R> double QEngineHIP<R>::ExpectationPauliSum(const std::vector<PauliTerm>& terms)
+{
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount);
+    return c.identity + pauliGroupsSum(c.groups);
+}
+
 template <typename R> std::pair<double, bitCapInt> QEngineHIP<R>::argMax()
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));

@@ -187,6 +187,15 @@ public:
     double ExpectationBitsFactorized(const std::vector<bitLenInt>& bits,
         const std::vector<bitCapInt>& perms, bitCapInt offset = 0) override;
     double VarianceBitsAll(const std::vector<bitLenInt>& bits, bitCapInt offset = 0) override;
+    // Pauli strings and sums: one read-only pass per distinct X/Y mask, no
+    // clone, no scratch, one host sync per call
+    double PauliExpectation(
+        const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
+    double ExpectationPauliAll(
+        const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
+    double VariancePauliAll(
+        const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
+    double ExpectationPauliSum(const std::vector<PauliTerm>& terms) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;
@@ -247,6 +256,10 @@ protected:
     void swapScratch(); // state <-> scratch
     void resizeState(bitCapInt nAmps, cplx<R>* newBuf); // replace buffer
     double reduceSum(int op, const ReduceArgs& a);
+    double pauliGroupsSum(const std::vector<PauliGroup>& groups);
+    // string with X/Y factors -> value; false when the generic lowering must answer
+    bool pauliStringNative(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
+        const char* what, double& value);
     std::pair<double, bitCapInt> argMax();
     std::vector<double> partProbs(bitLenInt start, bitLenInt length);
     bitCapInt sampleOnce(const std::vector<double>& chunkSums, bitCapInt chunkLen, double r,

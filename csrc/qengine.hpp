@@ -17,6 +17,92 @@
 
 namespace qrack_amd {
 
+// ---- Pauli-sum canonical form (shared by the dense engines) -----------------
+//
+// A Pauli string is (x, z, ny): x = mask of X/Y factors, z = mask of Z/Y
+// factors, ny = number of Y factors. P|i> = i^ny (-1)^popcount(i&z) |i^x>, so
+//   <psi|P|psi> = sum_i i^ny (-1)^popcount(i&z) conj(psi[i^x]) psi[i],
+// one read-only pass. Terms that share x differ only in a per-index weight
+// and share a pass; they are grouped here so engines cannot drift.
+struct PauliCanonTerm {
+    bitCapInt z;
+    double w; // coeff * i^ny, which is purely real or purely imaginary
+};
+
+struct PauliGroup {
+    bitCapInt x = 0;
+    std::vector<PauliCanonTerm> re; // ny even: weight w
+    std::vector<PauliCanonTerm> im; // ny odd: weight i*w
+};
+
+struct PauliCanonSum {
+    double identity = 0;            // summed coefficients of all-identity terms
+    std::vector<PauliGroup> groups; // ascending x; an x = 0 group comes first
+};
+
+// true when the string can take the one-pass path: every qubit in range and
+// none listed twice (callers fall back to the generic lowering otherwise)
+inline bool pauliStringMasks(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
+    bitLenInt qubitCount, bitCapInt& x, bitCapInt& z)
+{
+    x = 0;
+    z = 0;
+    bitCapInt seen = 0;
+    for (size_t i = 0; i < bits.size(); ++i) {
+        if (bits[i] >= qubitCount || bits[i] >= 64u || (unsigned)paulis[i] > 3u) return false;
+        const bitCapInt p = pow2(bits[i]);
+        if (seen & p) return false;
+        seen |= p;
+        // PauliX = 1, PauliZ = 2, PauliY = 3: bit 0 flips, bit 1 signs
+        if (paulis[i] & 1u) x |= p;
+        if (paulis[i] & 2u) z |= p;
+    }
+    return true;
+}
+
+// add coeff * (the string with sign mask z) to a group: weight coeff * i^ny
+inline void pauliGroupAdd(PauliGroup& g, bitCapInt z, double coeff)
+{
+    const int ny = __builtin_popcountll(g.x & z) & 3;
+    const double w = (ny & 2) ? -coeff : coeff; // i^2 = -1, i^3 = -i
+    ((ny & 1) ? g.im : g.re).push_back({ z, w });
+}
+
+inline PauliGroup pauliStringGroup(bitCapInt x, bitCapInt z, double coeff)
+{
+    PauliGroup g;
+    g.x = x;
+    pauliGroupAdd(g, z, coeff);
+    return g;
+}
+
+// Drop identities, merge equal (x, z), group by x. Terms are validated first.
+inline PauliCanonSum canonicalizePauliSum(const std::vector<PauliTerm>& terms, bitLenInt qubitCount)
+{
+    validatePauliTerms(terms, qubitCount);
+    std::map<std::pair<bitCapInt, bitCapInt>, double> merged;
+    PauliCanonSum out;
+    for (const PauliTerm& t : terms) {
+        bitCapInt x, z;
+        if (!pauliStringMasks(t.bits, t.paulis, qubitCount, x, z))
+            throw QrackError("ExpectationPauliSum: qubit out of range");
+        if (!x && !z) {
+            out.identity += t.coeff;
+        } else {
+            merged[{ x, z }] += t.coeff;
+        }
+    }
+    for (const auto& kv : merged) {
+        const bitCapInt x = kv.first.first, z = kv.first.second;
+        if (out.groups.empty() || out.groups.back().x != x) {
+            out.groups.emplace_back();
+            out.groups.back().x = x;
+        }
+        pauliGroupAdd(out.groups.back(), z, kv.second);
+    }
+    return out;
+}
+
 template <typename R> class QEngine;
 template <typename R> using QEnginePtr = std::shared_ptr<QEngine<R>>;
 

@@ -88,6 +88,14 @@ public:
     double ExpectationBitsFactorized(const std::vector<bitLenInt>& bits,
         const std::vector<bitCapInt>& perms, bitCapInt offset = 0) override;
     double VarianceBitsAll(const std::vector<bitLenInt>& bits, bitCapInt offset = 0) override;
+    // Pauli strings and sums: one read-only pass per distinct X/Y mask
+    double PauliExpectation(
+        const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
+    double ExpectationPauliAll(
+        const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
+    double VariancePauliAll(
+        const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
+    double ExpectationPauliSum(const std::vector<PauliTerm>& terms) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;
@@ -148,6 +156,9 @@ protected:
         bitCapInt controlMask, const std::function<bitCapInt(bitCapInt)>& f);
     bitCapInt SampleOnce();
     void QftColumn(bitLenInt start, bitLenInt col, int sign, bool pre);
+    double pauliGroupSum(const PauliGroup& g);
+    bool pauliStringNative(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
+        const char* what, double& value);
 
 };
 

@@ -170,6 +170,26 @@ public:
         FlushAll();
         return inner->VarianceBitsAll(b, o);
     }
+    double PauliExpectation(const std::vector<bitLenInt>& b, const std::vector<Pauli>& p) override
+    {
+        FlushAll();
+        return inner->PauliExpectation(b, p);
+    }
+    double ExpectationPauliAll(const std::vector<bitLenInt>& b, const std::vector<Pauli>& p) override
+    {
+        FlushAll();
+        return inner->ExpectationPauliAll(b, p);
+    }
+    double VariancePauliAll(const std::vector<bitLenInt>& b, const std::vector<Pauli>& p) override
+    {
+        FlushAll();
+        return inner->VariancePauliAll(b, p);
+    }
+    double ExpectationPauliSum(const std::vector<PauliTerm>& t) override
+    {
+        FlushAll();
+        return inner->ExpectationPauliSum(t);
+    }
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override { FlushAll(); return inner->TrySeparate(q); }

@@ -695,6 +695,14 @@ double QInterface<R>::PauliExpectation(
     return result;
 }
 
+template <typename R> double QInterface<R>::ExpectationPauliSum(const std::vector<PauliTerm>& terms)
+{
+    validatePauliTerms(terms, qubitCount);
+    double e = 0;
+    for (const PauliTerm& t : terms) e += t.coeff * PauliExpectation(t.bits, t.paulis);
+    return e;
+}
+
 // ---- ALU defaults ----------------------------------------------------------
 
 template <typename R> static void aluThrow()

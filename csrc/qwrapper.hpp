@@ -137,6 +137,22 @@ public:
     {
         return inner->VarianceBitsAll(b, o);
     }
+    double PauliExpectation(const std::vector<bitLenInt>& b, const std::vector<Pauli>& p) override
+    {
+        return inner->PauliExpectation(b, p);
+    }
+    double ExpectationPauliAll(const std::vector<bitLenInt>& b, const std::vector<Pauli>& p) override
+    {
+        return inner->ExpectationPauliAll(b, p);
+    }
+    double VariancePauliAll(const std::vector<bitLenInt>& b, const std::vector<Pauli>& p) override
+    {
+        return inner->VariancePauliAll(b, p);
+    }
+    double ExpectationPauliSum(const std::vector<PauliTerm>& t) override
+    {
+        return inner->ExpectationPauliSum(t);
+    }
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override { return inner->TrySeparate(q); }

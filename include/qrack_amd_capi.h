@@ -86,6 +86,10 @@ void qrack_set_permutation_wide(quid sid, uint64_t lo, uint64_t hi);
 void qrack_measure_shots_qubits(quid sid, const uint64_t* qubits, uint64_t nq, uint64_t shots,
     uint64_t* shotsArray);
 double qrack_joint_ensemble_probability(quid sid, const int* paulis, const uint64_t* qs, uint64_t n);
+/* sum_t coeffs[t] <P_t>: term t owns the next termLens[t] entries of qs / paulis
+ * (Pauli codes 0=I 1=X 2=Z 3=Y) */
+double qrack_expectation_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis);
 
 /* QFT */
 void qrack_qft(quid sid, uint64_t start, uint64_t length);

@@ -34,7 +34,12 @@ from qrack_amd._qrack import (  # noqa: F401
     __version__,
 )
 
+import qrack_amd._qrack as _qrack
+
 Pauli_I, Pauli_X, Pauli_Z, Pauli_Y = 0, 1, 2, 3
+# Pauli-sum terms sharing one X/Y mask that the HIP engine serves per launch
+# (0 when the extension was built without the HIP engine)
+PAULI_MAX_TERMS = getattr(_qrack, "PAULI_MAX_TERMS", 0)
 
 
 def create_simulator(

@@ -91,5 +91,47 @@ int main()
     auto dest = CreateStack<float>(2, { "cpu" }, 0, 3, -1, 1);
     c->Decompose(3, dest);
     std::printf("ok: lifecycle\n");
+    // QEngineCPU one-pass Pauli strings and sums: widths 1, 2, 5 and 13 (the
+    // last one is wide enough for the thread pool), every x-mask shape
+    for (bitLenInt n : { 1u, 2u, 5u, 13u }) {
+        auto p = CreateStack<float>(n, { "cpu" }, 0, 4, -1, 1);
+        for (bitLenInt i = 0; i < n; ++i) p->RY(0.3f + 0.1f * (float)i, i);
+        for (bitLenInt i = 0; i + 1 < n; ++i) p->CNOT(i, i + 1);
+        std::vector<PauliTerm> terms;
+        terms.push_back({ 0.5, {}, {} });
+        terms.push_back({ 1.0, { 0 }, { PauliX } });
+        terms.push_back({ -1.0, { n - 1 }, { PauliY } });
+        if (n > 1) {
+            terms.push_back({ 0.25, { n - 1, 0 }, { PauliZ, PauliI } });
+            terms.push_back({ 0.75, { 0, n - 1 }, { PauliY, PauliY } });
+            terms.push_back({ 0.75, { n - 1, 0 }, { PauliX, PauliX } });
+            terms.push_back({ 2.0, { 0, 1 }, { PauliZ, PauliZ } });
+        }
+        std::vector<bitLenInt> all;
+        std::vector<Pauli> mixed;
+        for (bitLenInt i = 0; i < n; ++i) {
+            all.push_back(i);
+            mixed.push_back((Pauli)(1 + i % 3));
+        }
+        terms.push_back({ 1.5, all, mixed });
+        terms.push_back({ 1.5, all, mixed }); // merges with the one before
+        const double e = p->ExpectationPauliSum(terms);
+        double ref = 0;
+        for (const PauliTerm& t : terms) ref += t.coeff * p->PauliExpectation(t.bits, t.paulis);
+        if (std::abs(e - ref) > 1e-5) {
+            std::printf("FAIL: pauli sum %u: %f vs %f\n", n, e, ref);
+            return 1;
+        }
+        (void)p->ExpectationPauliAll(all, mixed);
+        (void)p->VariancePauliAll(all, mixed);
+        (void)p->PauliExpectation({ 0, 0 }, { PauliX, PauliZ }); // repeated qubit: generic path
+        try {
+            (void)p->ExpectationPauliSum({ { 1.0, { n }, { PauliX } } });
+            std::printf("FAIL: out-of-range qubit accepted\n");
+            return 1;
+        } catch (const QrackError&) {
+        }
+    }
+    std::printf("ok: pauli sum\n");
     return 0;
 }
