@@ -125,27 +125,43 @@ void ParallelFor::par_for_skip(bitCapInt maxI, bitCapInt skipPower, ParallelFunc
     });
 }
 
+// Compensated accumulator. A probability sum feeds the 1/sqrt(prob) factor of
+// a collapse or normalisation: the ~sqrt(N) eps drift of a plain double
+// accumulation would rescale an fp64 state by that much.
+namespace {
+struct KahanSum {
+    double sum = 0, comp = 0;
+    void add(double x)
+    {
+        const double y = x - comp;
+        const double t = sum + y;
+        comp = (t - sum) - y;
+        sum = t;
+    }
+};
+} // namespace
+
 double ParallelFor::par_sum(bitCapInt maxI, const std::function<double(const bitCapInt&)>& fn) const
 {
     if (maxI < (pStride_ << 1u)) {
-        double s = 0;
-        for (bitCapInt i = 0; i < maxI; ++i) s += fn(i);
-        return s;
+        KahanSum s;
+        for (bitCapInt i = 0; i < maxI; ++i) s.add(fn(i));
+        return s.sum;
     }
     const unsigned nw = (unsigned)std::min<bitCapInt>(numCores(), (maxI + pStride_ - 1) / pStride_);
     std::vector<double> partials(nw, 0.0);
     std::atomic<bitCapInt> next(0);
     const bitCapInt stride = pStride_;
     ThreadPool::instance().run(nw, [&](unsigned w) {
-        double s = 0;
+        KahanSum s;
         for (;;) {
             const bitCapInt chunk = next.fetch_add(1, std::memory_order_relaxed);
             const bitCapInt lo = chunk * stride;
             if (lo >= maxI) break;
             const bitCapInt hi = std::min(maxI, lo + stride);
-            for (bitCapInt i = lo; i < hi; ++i) s += fn(i);
+            for (bitCapInt i = lo; i < hi; ++i) s.add(fn(i));
         }
-        partials[w] = s;
+        partials[w] = s.sum;
     });
     double total = 0;
     for (double p : partials) total += p;

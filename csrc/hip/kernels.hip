@@ -925,6 +925,26 @@ void launchPermute(const cplx<R>* sv, cplx<R>* nsv, const PermArgs& a, hipStream
     hipLaunchKernelGGL((k_permute<R>), dim3(gridFor(a.maxI)), dim3(QA_BLOCK), 0, stream, sv, nsv, a);
 }
 
+// start vector for the controlled multiply family: the state with the
+// fully-controlled subspace cleared (k_permute then fills that subspace)
+template <typename R>
+__global__ void k_copy_uncontrolled(
+    const cplx<R>* sv, cplx<R>* nsv, bitCapInt maxQPower, bitCapInt controlMask)
+{
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt i = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; i < maxQPower; i += stride) {
+        nsv[i] = ((i & controlMask) == controlMask) ? cplx<R>(0, 0) : sv[i];
+    }
+}
+
+template <typename R>
+void launchCopyUncontrolled(
+    const cplx<R>* sv, cplx<R>* nsv, bitCapInt maxQPower, bitCapInt controlMask, hipStream_t stream)
+{
+    hipLaunchKernelGGL((k_copy_uncontrolled<R>), dim3(gridFor(maxQPower)), dim3(QA_BLOCK), 0, stream,
+        sv, nsv, maxQPower, controlMask);
+}
+
 template <typename R>
 __global__ void k_phaseflipless(cplx<R>* sv, bitCapInt maxQPower, bitCapInt greaterPerm,
     bitLenInt start, bitCapInt regMask, bitCapInt flagMask)
@@ -3348,6 +3368,8 @@ void launchPauliGroup(const cplx<R>* sv, const PauliArgs& a, double* partialsDev
         const cplx<R>*, cplx<R>*, bitCapInt, bitLenInt, bitLenInt, hipStream_t);                    \
     template void launchShuffleSwap<R>(cplx<R>*, cplx<R>*, bitCapInt, hipStream_t);                 \
     template void launchPermute<R>(const cplx<R>*, cplx<R>*, const PermArgs&, hipStream_t);         \
+    template void launchCopyUncontrolled<R>(                                                        \
+        const cplx<R>*, cplx<R>*, bitCapInt, bitCapInt, hipStream_t);                               \
     template void launchPhaseFlipIfLess<R>(                                                         \
         cplx<R>*, bitCapInt, bitCapInt, bitLenInt, bitCapInt, bitCapInt, hipStream_t);              \
     template void launchChunkSums<R>(const cplx<R>*, bitCapInt, bitCapInt, double*, hipStream_t);   \

@@ -181,6 +181,11 @@ void launchShuffleSwap(cplx<R>* aHigh, cplx<R>* bLow, bitCapInt half, hipStream_
 template <typename R>
 void launchPermute(const cplx<R>* sv, cplx<R>* nsv, const PermArgs& a, hipStream_t stream);
 
+// nsv[i] = ((i & controlMask) == controlMask) ? 0 : sv[i]
+template <typename R>
+void launchCopyUncontrolled(
+    const cplx<R>* sv, cplx<R>* nsv, bitCapInt maxQPower, bitCapInt controlMask, hipStream_t stream);
+
 template <typename R>
 void launchPhaseFlipIfLess(cplx<R>* sv, bitCapInt maxQPower, bitCapInt greaterPerm, bitLenInt start,
     bitCapInt regMask, bitCapInt flagMask, hipStream_t stream);

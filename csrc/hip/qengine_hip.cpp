@@ -1226,8 +1226,15 @@ template <typename R> double QEngineHIP<R>::reduceSum(int op, const ReduceArgs& 
     QA_HIP_CHECK(hipMemcpyAsync(
         hPartials.data(), dPartials, grid * sizeof(double), hipMemcpyDeviceToHost, stream));
     Finish();
-    double s = 0;
-    for (int i = 0; i < grid; ++i) s += hPartials[i];
+    // compensated sum: up to QA_REDUCE_MAX_BLOCKS partials, and a plain
+    // accumulation of that many drifts by several eps of an fp64 result
+    double s = 0, comp = 0;
+    for (int i = 0; i < grid; ++i) {
+        const double y = hPartials[i] - comp;
+        const double t = s + y;
+        comp = (t - s) - y;
+        s = t;
+    }
     return s;
 }
 
@@ -1776,7 +1783,11 @@ template <typename R> void QEngineHIP<R>::permuteOp(PermArgs& a, bool partialSpa
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("alu_permute", stream);
     ensureScratch();
-    if (copyFirst) {
+    if (copyFirst && partialSpace) {
+        // controlled op over a sub-domain of the controlled subspace (carry/out
+        // register |0>): sources that are nobody's destination must not survive
+        launchCopyUncontrolled<R>(rState(), dScratch, maxQPower, a.controlMask, stream);
+    } else if (copyFirst) {
         QA_HIP_CHECK(hipMemcpyAsync(
             dScratch, rState(), sizeof(cplx<R>) * maxQPower, hipMemcpyDeviceToDevice, stream));
     } else if (partialSpace) {

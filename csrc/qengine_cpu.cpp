@@ -997,7 +997,8 @@ template <typename R>
 void QEngineCPU<R>::ControlledPermutationOp(
     bitCapInt controlMask, const std::function<bitCapInt(bitCapInt)>& f)
 {
-    // copy, then remap the control-set subspace (f preserves control bits)
+    // copy, then remap the control-set subspace (f preserves control bits
+    // and is a bijection on that whole subspace, so every slot is rewritten)
     std::vector<cplx<R>> nStateVec(stateVec);
     const cplx<R>* sv = stateVec.data();
     cplx<R>* nsv = nStateVec.data();
@@ -1005,6 +1006,17 @@ void QEngineCPU<R>::ControlledPermutationOp(
         if ((i & controlMask) == controlMask) nsv[f(i)] = sv[i];
     });
     stateVec = std::move(nStateVec);
+}
+
+template <typename R> std::vector<cplx<R>> QEngineCPU<R>::UncontrolledCopy(bitCapInt controlMask)
+{
+    std::vector<cplx<R>> nStateVec(maxQPower);
+    const cplx<R>* sv = stateVec.data();
+    cplx<R>* nsv = nStateVec.data();
+    this->par_for(0, maxQPower, [sv, nsv, controlMask](const bitCapInt& i, unsigned) {
+        nsv[i] = ((i & controlMask) == controlMask) ? cplx<R>(0, 0) : sv[i];
+    });
+    return nStateVec;
 }
 
 // ---- ALU -------------------------------------------------------------------
@@ -1335,7 +1347,7 @@ void QEngineCPU<R>::CMUL(bitCapInt toMul, bitLenInt inOutStart, bitLenInt carryS
     for (bitLenInt i = 0; i < length; ++i) skipPowers.push_back(pow2(carryStart + i));
     for (bitLenInt c : controls) skipPowers.push_back(pow2(c));
     std::sort(skipPowers.begin(), skipPowers.end());
-    std::vector<cplx<R>> nStateVec(stateVec);
+    std::vector<cplx<R>> nStateVec = UncontrolledCopy(controlMask);
     const cplx<R>* sv = stateVec.data();
     cplx<R>* nsv = nStateVec.data();
     this->par_for_mask(
@@ -1369,7 +1381,7 @@ void QEngineCPU<R>::CDIV(bitCapInt toDiv, bitLenInt inOutStart, bitLenInt carryS
     for (bitLenInt i = 0; i < length; ++i) skipPowers.push_back(pow2(carryStart + i));
     for (bitLenInt c : controls) skipPowers.push_back(pow2(c));
     std::sort(skipPowers.begin(), skipPowers.end());
-    std::vector<cplx<R>> nStateVec(stateVec);
+    std::vector<cplx<R>> nStateVec = UncontrolledCopy(controlMask);
     const cplx<R>* sv = stateVec.data();
     cplx<R>* nsv = nStateVec.data();
     this->par_for_mask(
@@ -1402,7 +1414,7 @@ void QEngineCPU<R>::CMULModNOut(bitCapInt toMul, bitCapInt modN, bitLenInt inSta
     for (bitLenInt i = 0; i < length; ++i) skipPowers.push_back(pow2(outStart + i));
     for (bitLenInt c : controls) skipPowers.push_back(pow2(c));
     std::sort(skipPowers.begin(), skipPowers.end());
-    std::vector<cplx<R>> nStateVec(stateVec);
+    std::vector<cplx<R>> nStateVec = UncontrolledCopy(controlMask);
     const cplx<R>* sv = stateVec.data();
     cplx<R>* nsv = nStateVec.data();
     this->par_for_mask(
@@ -1433,7 +1445,7 @@ void QEngineCPU<R>::CIMULModNOut(bitCapInt toMul, bitCapInt modN, bitLenInt inSt
     for (bitLenInt i = 0; i < length; ++i) skipPowers.push_back(pow2(outStart + i));
     for (bitLenInt c : controls) skipPowers.push_back(pow2(c));
     std::sort(skipPowers.begin(), skipPowers.end());
-    std::vector<cplx<R>> nStateVec(stateVec);
+    std::vector<cplx<R>> nStateVec = UncontrolledCopy(controlMask);
     const cplx<R>* sv = stateVec.data();
     cplx<R>* nsv = nStateVec.data();
     this->par_for_mask(
@@ -1464,7 +1476,7 @@ void QEngineCPU<R>::CPOWModNOut(bitCapInt base, bitCapInt modN, bitLenInt inStar
     for (bitLenInt i = 0; i < length; ++i) skipPowers.push_back(pow2(outStart + i));
     for (bitLenInt c : controls) skipPowers.push_back(pow2(c));
     std::sort(skipPowers.begin(), skipPowers.end());
-    std::vector<cplx<R>> nStateVec(stateVec);
+    std::vector<cplx<R>> nStateVec = UncontrolledCopy(controlMask);
     const cplx<R>* sv = stateVec.data();
     cplx<R>* nsv = nStateVec.data();
     this->par_for_mask(

@@ -154,6 +154,10 @@ protected:
     void PermutationOp(const std::function<bitCapInt(bitCapInt)>& f);
     void ControlledPermutationOp(
         bitCapInt controlMask, const std::function<bitCapInt(bitCapInt)>& f);
+    // Copy of the state with the fully-controlled subspace cleared: the start
+    // vector for controlled ops that map a sub-domain (carry/out register |0>)
+    // of that subspace, so no unmapped source slot keeps a stale amplitude.
+    std::vector<cplx<R>> UncontrolledCopy(bitCapInt controlMask);
     bitCapInt SampleOnce();
     void QftColumn(bitLenInt start, bitLenInt col, int sign, bool pre);
     double pauliGroupSum(const PauliGroup& g);

@@ -20,6 +20,14 @@ def set_reg(q, start, length, value):
             q.x(start + i)
 
 
+def assert_one_basis_state(q):
+    """A permutation op on a basis state leaves one amplitude, of norm 1:
+    the measured register alone cannot see a stale copy left behind."""
+    sv = np.asarray(q.get_state_vector())
+    assert np.count_nonzero(sv) == 1
+    assert abs(np.linalg.norm(sv) - 1.0) < 1e-6
+
+
 def test_inc_dec_basis():
     q = make(4)
     set_reg(q, 0, 4, 5)
@@ -125,6 +133,7 @@ def test_cmul():
     assert q.m_reg(0, 6) == 3
     q.x(6)
     q.cmul(5, 0, 3, 3, [6])
+    assert_one_basis_state(q)
     r = q.m_reg(0, 6)
     assert r == 15
 
@@ -134,6 +143,7 @@ def test_cpow_mod_n_out():
     set_reg(q, 0, 4, 2)
     q.x(8)
     q.cpow_mod_n_out(7, 15, 0, 4, 4, [8])  # 7^2 mod 15 = 4
+    assert_one_basis_state(q)
     r = q.m_reg(4, 4)
     assert r == 4
 
