@@ -21,6 +21,7 @@
 #ifdef QRACK_AMD_HIP_ENGINE
 #include "hip/qengine_hip.hpp"
 #endif
+#include "hip/qft_plan.hpp"
 
 namespace py = pybind11;
 using namespace qrack_amd;
@@ -847,6 +848,29 @@ PYBIND11_MODULE(_qrack, m)
         py::arg("pages_per_device") = (bitLenInt)1, py::arg("devices") = std::vector<int64_t>{});
 
     m.def("hip_device_count", &HipDeviceCount);
+    // the HIP engine's QFT schedule for a start-0 register, top pass first,
+    // as (kind, colLo, nCols) with kind "low" | "mid" | "col"; needs no GPU
+    m.def(
+        "qft_pass_plan",
+        [](int length, int width, const std::string& precision, int midmax) {
+            if (precision != "fp32" && precision != "fp64") {
+                throw std::invalid_argument("qft_pass_plan: precision must be fp32 or fp64");
+            }
+            if (length < 0 || width < length) {
+                throw std::invalid_argument("qft_pass_plan: need 0 <= length <= width");
+            }
+            QftPlanOpts o;
+            o.midMax = midmax;
+            py::list out;
+            for (const QftPass& p : qftPassPlan(length, 0, width, precision == "fp32" ? 4 : 8, o)) {
+                const char* kind = p.kind == QftPassKind::Low ? "low"
+                    : p.kind == QftPassKind::Mid              ? "mid"
+                                                              : "col";
+                out.append(py::make_tuple(kind, p.colLo, p.nCols));
+            }
+            return out;
+        },
+        py::arg("length"), py::arg("width"), py::arg("precision"), py::arg("midmax") = 9);
 #ifdef QRACK_AMD_HIP_ENGINE
     m.def("profile_report", []() {
         py::dict d;

@@ -12,7 +12,10 @@
 //    branch is wave-uniform) instead of 26 near-identical kernels.
 #include "kernels.hpp"
 
+#include <algorithm>
 #include <cstdlib>
+#include <mutex>
+#include <vector>
 
 namespace qrack_amd {
 
@@ -2340,6 +2343,197 @@ void launchQftMidLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols
     } else {
         launchQftMidLdsBasisK<R, 2>(
             sv, nTiles, grid, ldsBytes, colLo, nCols, piSign, pre, perm, phase, stream);
+    }
+}
+
+// Wide-tile mid pass: 2^LB contiguous low amplitudes x 2^nCols column-bit
+// combinations, LB < 6, so a tile of the same LDS footprint carries more
+// columns (LB = 4: 9 columns in 64 KB, 128-byte runs). A sibling of
+// k_qft_mid_lds / qftMidGroup rather than a shared template: its LDS
+// addressing differs (below) and the 64-wide kernels stay exactly as they
+// compile today. Ramp arithmetic is the 64-wide kernel's with the split
+// moved: `low` is the LB in-run bits, midFixed the tile-constant bits
+// LB..colLo-1, cbBelow the tile's below-group column bits.
+//
+// LDS mapping: amplitude (cb, low) of the tile, cb = the nCols column bits,
+// lives at element ((cb ^ ((cb >> K) & SW)) << LB) | low, SW = 2^(6-LB) - 1.
+// A wave's 64 lanes cover 2^(6-LB) consecutive orbit rows cbr. In the
+// gLo = 0 group those rows differ in cb bits K.. (cb = cbr << K | b), which
+// unswizzled puts them a multiple of 2^(K+LB) elements apart, all on the
+// same banks; XORing cb bits K.. into cb bits 0.. spreads them over
+// 2^(6-LB) consecutive 2^LB-element rows, i.e. 64 distinct consecutive
+// 8-byte elements per wave access. In the gLo >= K groups the rows already
+// differ in cb bits 0.. and the XORed-in bits are group bits, the same for
+// every lane of one access, so those stay conflict-free too. Bits K.. of cb
+// are untouched, so the mapping is a bijection of the tile.
+template <int K, int LB> __device__ __forceinline__ int qaWideRow(int cb)
+{
+    return (cb ^ ((cb >> K) & ((1 << (6 - LB)) - 1))) << LB;
+}
+
+template <typename R, int K, bool PRE, bool BASIS, int LB, int THREADS>
+__device__ __forceinline__ void qftMidGroupWide(cplx<R>* sv, cplx<R>* lds, bitCapInt xBase,
+    int colLo, int tileAmps, int gLo, R midFixed, R hbScale, R scaleHi, R iSign,
+    bool fromGlobal, bool toGlobal, bitCapInt perm, cplx<R> phase)
+{
+    constexpr int NS = 1 << K;
+    const int orbitCount = tileAmps >> K;
+    for (int o = threadIdx.x; o < orbitCount; o += THREADS) {
+        const int low = o & ((1 << LB) - 1);
+        const int cbr = o >> LB;
+        const int cbBelow = cbr & ((1 << gLo) - 1);
+        const int cb0 = ((cbr >> gLo) << (gLo + K)) | cbBelow;
+        cplx<R> v[NS];
+        if (fromGlobal) {
+            if (BASIS) {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) {
+                    v[b] = qaOpaque<R>(
+                        ((xBase | ((bitCapInt)(cb0 | (b << gLo)) << colLo) | (bitCapInt)low) == perm)
+                            ? phase
+                            : cplx<R>{ (R)0, (R)0 });
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) {
+                    v[b] = sv[xBase | ((bitCapInt)(cb0 | (b << gLo)) << colLo) | (bitCapInt)low];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < NS; ++b) v[b] = lds[qaWideRow<K, LB>(cb0 | (b << gLo)) | low];
+        }
+        R sn, cs;
+        devSinCos<R>(scaleHi * ((R)low + midFixed + hbScale * (R)cbBelow), &sn, &cs);
+        qftOrbitColumns<R, K, PRE>(v, iSign, cplx<R>{ cs, sn });
+        if (toGlobal) {
+#pragma unroll
+            for (int b = 0; b < NS; ++b) {
+                sv[xBase | ((bitCapInt)(cb0 | (b << gLo)) << colLo) | (bitCapInt)low] = v[b];
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < NS; ++b) lds[qaWideRow<K, LB>(cb0 | (b << gLo)) | low] = v[b];
+        }
+    }
+}
+
+// nCols = 9 (K = 3, three groups) or 8 (K = 4, two groups) mid columns per
+// pass; THREADS threads per block, one 2^(LB+nCols)-amplitude tile at a
+// time. BASIS: first pass from the basis state phase·|perm>, write-only,
+// stores bit-identical to the normal instantiation (see k_qft_mid_lds_basis).
+// Requires a start-0 register, colLo >= LB and nCols a multiple of K.
+template <typename R, int K, bool PRE, bool BASIS, int LB, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_qft_mid_wide(
+    cplx<R>* sv, bitCapInt nTiles, int colLo, int nCols, R piSign, bitCapInt perm, cplx<R> phase)
+{
+    extern __shared__ unsigned char qa_lds_raw3[];
+    cplx<R>* lds = reinterpret_cast<cplx<R>*>(qa_lds_raw3);
+    const int tileAmps = (1 << LB) << nCols;
+    const int nG = nCols / K;
+    const bitCapInt midMask = (ONE_BCI << (colLo - LB)) - 1u;
+    const R hbScale = (R)(uint64_t)(ONE_BCI << colLo);
+    const R iSign = (piSign >= 0) ? (R)1 : (R)-1;
+    for (bitCapInt t = blockIdx.x; t < nTiles; t += gridDim.x) {
+        const bitCapInt xBase =
+            ((t >> (colLo - LB)) << (colLo + nCols)) | ((t & midMask) << LB);
+        const R midFixed = (R)(uint64_t)((t & midMask) << LB);
+        for (int gi = 0; gi < nG; ++gi) {
+            const int g = PRE ? gi : (nG - 1 - gi);
+            const int gLo = K * g;
+            const bool fromGlobal = (gi == 0);
+            const bool toGlobal = (gi == nG - 1);
+            const R scaleHi = piSign / (R)(ONE_BCI << (colLo + gLo + K - 1));
+            if (gi != 0) __syncthreads();
+            qftMidGroupWide<R, K, PRE, BASIS, LB, THREADS>(sv, lds, xBase, colLo, tileAmps, gLo,
+                midFixed, hbScale, scaleHi, iSign, fromGlobal, toGlobal, perm, phase);
+        }
+        __syncthreads();
+    }
+}
+
+template <typename R, int K, bool PRE, bool BASIS, int LB, int THREADS>
+static void launchQftMidWideOne(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols, R piSign,
+    bitCapInt perm, cplx<R> phase, hipStream_t stream)
+{
+    const bitCapInt nTiles = maxQPower >> (LB + nCols);
+    const size_t ldsBytes = (size_t(1) << (LB + nCols)) * sizeof(cplx<R>);
+    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    auto kern = k_qft_mid_wide<R, K, PRE, BASIS, LB, THREADS>;
+    if (ldsBytes >= 64u * 1024u) {
+        // a tile at or above the default dynamic-LDS limit: raise it, once
+        // per instantiation and device
+        static std::mutex mtx;
+        static std::vector<int> raised;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) throw QrackError("k_qft_mid_wide: no device");
+        std::lock_guard<std::mutex> lock(mtx);
+        if (std::find(raised.begin(), raised.end(), dev) == raised.end()) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes) != hipSuccess) {
+                throw QrackError("k_qft_mid_wide: cannot raise the dynamic LDS limit");
+            }
+            raised.push_back(dev);
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), ldsBytes, stream, sv, nTiles, colLo, nCols,
+        piSign, perm, phase);
+}
+
+template <typename R, bool BASIS, int LB>
+static void launchQftMidWideLB(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols, R piSign,
+    bool pre, bitCapInt perm, cplx<R> phase, hipStream_t stream)
+{
+    // 9 columns: K = 3, two orbits per thread; 8 columns: K = 4, one orbit
+    // per thread of a block half the size
+    constexpr int T9 = 32 << LB;
+    constexpr int T8 = 16 << LB;
+    if (nCols == 9) {
+        if (pre) {
+            launchQftMidWideOne<R, 3, true, BASIS, LB, T9>(
+                sv, maxQPower, colLo, nCols, piSign, perm, phase, stream);
+        } else {
+            launchQftMidWideOne<R, 3, false, BASIS, LB, T9>(
+                sv, maxQPower, colLo, nCols, piSign, perm, phase, stream);
+        }
+    } else if (nCols == 8) {
+        if (pre) {
+            launchQftMidWideOne<R, 4, true, BASIS, LB, T8>(
+                sv, maxQPower, colLo, nCols, piSign, perm, phase, stream);
+        } else {
+            launchQftMidWideOne<R, 4, false, BASIS, LB, T8>(
+                sv, maxQPower, colLo, nCols, piSign, perm, phase, stream);
+        }
+    } else {
+        throw QrackError("launchQftMidWide: nCols must be 8 or 9");
+    }
+}
+
+void launchQftMidWide(cplx<float>* sv, bitCapInt maxQPower, int lowBits, int colLo, int nCols,
+    int sign, bool pre, bool basis, bitCapInt perm, cplx<float> phase, hipStream_t stream)
+{
+    if (colLo < lowBits || (maxQPower >> (colLo + nCols)) == 0u) {
+        throw QrackError("launchQftMidWide: columns outside the state or below the run length");
+    }
+    const float piSign = (float)sign * 3.14159265358979323846f;
+    if (lowBits == 4) {
+        if (basis) {
+            launchQftMidWideLB<float, true, 4>(
+                sv, maxQPower, colLo, nCols, piSign, pre, perm, phase, stream);
+        } else {
+            launchQftMidWideLB<float, false, 4>(
+                sv, maxQPower, colLo, nCols, piSign, pre, perm, phase, stream);
+        }
+    } else if (lowBits == 5) {
+        if (basis) {
+            launchQftMidWideLB<float, true, 5>(
+                sv, maxQPower, colLo, nCols, piSign, pre, perm, phase, stream);
+        } else {
+            launchQftMidWideLB<float, false, 5>(
+                sv, maxQPower, colLo, nCols, piSign, pre, perm, phase, stream);
+        }
+    } else {
+        throw QrackError("launchQftMidWide: lowBits must be 4 or 5");
     }
 }
 

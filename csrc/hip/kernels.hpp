@@ -235,7 +235,9 @@ void launchQftLowLds(
     cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, int sign, bool pre, hipStream_t stream);
 
 // nCols mid-range QFT columns per pass through a 2D LDS tile (64 contiguous
-// low amps x 2^nCols column-bit combos; start-0 registers, colLo >= 6)
+// low amps x 2^nCols column-bit combos; start-0 registers, colLo >= 6).
+// nCols in {2, 3, 4, 6}: 32 KB of LDS at 6 columns fp32. More columns per
+// pass go through launchQftMidWide; the planner in qft_plan.hpp chooses.
 template <typename R>
 void launchQftMidLds(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols, int sign, bool pre,
     hipStream_t stream);
@@ -251,6 +253,20 @@ void launchQftLowLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, 
 template <typename R>
 void launchQftMidLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols, int sign,
     bool pre, bitCapInt perm, cplx<R> phase, hipStream_t stream);
+
+// Wide-tile mid pass, fp32 only: nCols = 9 (three K=3 orbit groups) or 8
+// (two K=4 groups) columns colLo..colLo+nCols-1 through a 2D LDS tile of
+// 2^lowBits contiguous low amplitudes x 2^nCols column-bit combinations.
+// lowBits = 4: 128-byte runs, 64 KB (9 columns, 512 threads) or 32 KB (8
+// columns, 256 threads) of LDS per block; lowBits = 5: 256-byte runs,
+// 128 KB / 64 KB, 1024 / 512 threads. Tiles of 64 KB and more have the
+// kernel's dynamic-LDS limit raised on first use. Requires a start-0
+// register, colLo >= lowBits and maxQPower >= 2^(colLo+nCols). basis: the
+// source is phase·|perm> and the buffer is undefined, as in
+// launchQftMidLdsBasis (write-only, stores bit-identical to basis = false
+// run on the materialised state); perm and phase are ignored otherwise.
+void launchQftMidWide(cplx<float>* sv, bitCapInt maxQPower, int lowBits, int colLo, int nCols,
+    int sign, bool pre, bool basis, bitCapInt perm, cplx<float> phase, hipStream_t stream);
 
 // forward low ladder that also writes tileSumsDev[t] = sum |amp|^2 of the
 // 2^tb amplitudes it stored for tile t (maxQPower >> tb doubles; fixed

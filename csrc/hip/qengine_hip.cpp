@@ -1,5 +1,6 @@
 // qrack_amd — HIP engine host implementation (see qengine_hip.hpp).
 #include "qengine_hip.hpp"
+#include "qft_plan.hpp"
 
 #include <set>
 
@@ -980,239 +981,174 @@ void QEngineHIP<R>::PhaseRampGeneral(R scale, bitLenInt rampStart, bitCapInt inP
     launchPhaseRampGeneral<R>(wState(), maxQPower, a, stream);
 }
 
+// environment switches of the QFT schedule, read once per process
+static const QftPlanOpts& qftPlanOpts()
+{
+    static const QftPlanOpts opts = []() {
+        QftPlanOpts o;
+        if (const char* env = std::getenv("QRACK_GPU_QFT_FUSE2")) {
+            o.fuseMax = std::atoi(env) != 0 ? 3 : 1;
+        } else if (const char* env = std::getenv("QRACK_GPU_QFT_FUSE")) {
+            o.fuseMax = std::atoi(env);
+        }
+        if (const char* env = std::getenv("QRACK_GPU_QFT_LDS")) o.ldsLow = std::atoi(env) != 0;
+        // fp64 mid groups would need tiles twice the size; the K4 fusion
+        // path serves fp64 there, so the planner keeps mid-LDS fp32-only
+        if (const char* env = std::getenv("QRACK_GPU_QFT_MIDLDS")) o.ldsMid = std::atoi(env) != 0;
+        // most columns in one mid pass: 9 and 8 allow the wide-tile kernel,
+        // 7 and below leave the six-at-a-time schedule
+        if (const char* env = std::getenv("QRACK_GPU_QFT_MIDMAX")) o.midMax = std::atoi(env);
+        // contiguous-run bits of the wide tile (4 or 5)
+        if (const char* env = std::getenv("QRACK_GPU_QFT_WIDELB")) {
+            o.wideLowBits = std::atoi(env) == 5 ? 5 : 4;
+        }
+        return o;
+    }();
+    return opts;
+}
+
 template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length, bool)
 {
-    // per column, ONE fully-fused kernel applies H and the column's entire
-    // controlled-phase ladder (exp(i*pi*(x mod 2^i)/2^i) on the H output's
-    // bit-set half) — a single state pass per column
+    // Walks the planner's pass list (qft_plan.hpp) top column first. Every
+    // pass is one trip over the state: a low ladder or mid pass through LDS
+    // tiles, or up to five columns fused in registers, each applying H and
+    // the columns' entire controlled-phase ladders
+    // (exp(i*pi*(x mod 2^i)/2^i) on the H output's bit-set half).
     if (!length) return;
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    static const int fuseMax = []() {
-        if (const char* env = std::getenv("QRACK_GPU_QFT_FUSE2")) {
-            return std::atoi(env) != 0 ? 3 : 1;
-        }
-        if (const char* env = std::getenv("QRACK_GPU_QFT_FUSE")) return std::atoi(env);
-        return 4;
-    }();
-    static const bool ldsLow = []() {
-        if (const char* env = std::getenv("QRACK_GPU_QFT_LDS")) return std::atoi(env) != 0;
-        return true;
-    }();
-    static const bool ldsMid = []() {
-        // fp64 mid groups would need 64 KB LDS tiles (2 blocks/CU); the K4
-        // fusion path serves fp64 as well there, so mid-LDS is fp32-only
-        if (sizeof(R) != 4) return false;
-        if (const char* env = std::getenv("QRACK_GPU_QFT_MIDLDS")) return std::atoi(env) != 0;
-        return true;
-    }();
+    const QftPlanOpts& opts = qftPlanOpts();
     const int tb = qaLdsTileBits<R>();
-    bitLenInt i = length;
-    while (i > 0) {
-        const bitLenInt col = i - 1u;
-        if (ldsLow && start == 0u && (bitLenInt)i <= (bitLenInt)tb &&
-            maxQPower >= (ONE_BCI << tb)) {
-            const bitLenInt AK = (bitLenInt)qaLowLadderK<R>();
-            const bitLenInt r = i % AK;
-            if (!r) {
-                // the whole remaining (K-aligned) ladder in ONE LDS pass of
-                // uniform register-orbit groups
-                HipProfScope prof("qft_low_lds", stream);
-                if (basisPending_) {
-                    // first pass from a pending basis state: write-only
-                    launchQftLowLdsBasis<R>(wStateAll(), maxQPower, tb, (int)col, +1, false,
-                        basisPerm_, basisPhase_, stream);
-                } else if (tileSumsUsable() && maxQPower >= (ONE_BCI << (tb + 11))) {
-                    // final pass: leave per-tile norms for the sampler (used
-                    // once a sampling chunk spans at least one tile)
-                    double* sums = tileSumsBuffer();
-                    launchQftLowLdsSums<R>(wState(), maxQPower, tb, (int)col, sums, stream);
-                    tileSumsValid_ = true;
-                } else {
-                    launchQftLowLds<R>(wState(), maxQPower, tb, (int)col, +1, false, stream);
-                }
-                break;
+    for (const QftPass& p : qftPassPlan((int)length, (int)start, (int)qubitCount, (int)sizeof(R), opts)) {
+        const bitLenInt lo = (bitLenInt)p.colLo;
+        const bitLenInt col = (bitLenInt)(p.colLo + p.nCols - 1);
+        if (p.kind == QftPassKind::Low) {
+            // the whole remaining (K-aligned) ladder in ONE LDS pass of
+            // uniform register-orbit groups
+            HipProfScope prof("qft_low_lds", stream);
+            if (basisPending_) {
+                // first pass from a pending basis state: write-only
+                launchQftLowLdsBasis<R>(wStateAll(), maxQPower, tb, (int)col, +1, false,
+                    basisPerm_, basisPhase_, stream);
+            } else if (tileSumsUsable() && maxQPower >= (ONE_BCI << (tb + 11))) {
+                // final pass: leave per-tile norms for the sampler (used
+                // once a sampling chunk spans at least one tile)
+                double* sums = tileSumsBuffer();
+                launchQftLowLdsSums<R>(wState(), maxQPower, tb, (int)col, sums, stream);
+                tileSumsValid_ = true;
+            } else {
+                launchQftLowLds<R>(wState(), maxQPower, tb, (int)col, +1, false, stream);
             }
-            if (i != r) {
-                // peel the top r columns so the ladder below is 4-aligned
-                if (r == 3u) {
-                    HipProfScope prof("qft_column3", stream);
-                    launchQftColumn3<R>(wState(), maxQPower, start, col, pow2(start + col),
-                        pow2(start + col - 1u), pow2(start + col - 2u), +1, false, stream);
-                } else if (r == 2u) {
-                    HipProfScope prof("qft_column2", stream);
-                    launchQftColumn2<R>(wState(), maxQPower, start, col, pow2(start + col),
-                        pow2(start + col - 1u), +1, false, stream);
+        } else if (p.kind == QftPassKind::Mid) {
+            HipProfScope prof("qft_mid_lds", stream);
+            if (p.nCols >= QA_QFT_WIDE_MIN_COLS) {
+                if constexpr (sizeof(R) == 4) {
+                    const bool basis = basisPending_;
+                    cplx<R>* sv = basis ? wStateAll() : wState();
+                    launchQftMidWide(sv, maxQPower, opts.wideLowBits, p.colLo, p.nCols, +1, false,
+                        basis, basisPerm_, basisPhase_, stream);
                 } else {
-                    HipProfScope prof("qft_column", stream);
-                    launchQftColumn<R>(
-                        wState(), maxQPower, start, col, pow2(start + col), +1, false, stream);
+                    throw QrackError("QFT: wide mid pass planned for a non-fp32 engine");
                 }
-                i -= r;
-                continue;
+            } else if (basisPending_) {
+                launchQftMidLdsBasis<R>(wStateAll(), maxQPower, p.colLo, p.nCols, +1, false,
+                    basisPerm_, basisPhase_, stream);
+            } else {
+                launchQftMidLds<R>(wState(), maxQPower, p.colLo, p.nCols, +1, false, stream);
             }
-            // i < 4: the small fused kernels below finish the register
-        }
-        if (ldsLow && ldsMid && start == 0u && (bitLenInt)i > (bitLenInt)tb &&
-            maxQPower >= (ONE_BCI << tb)) {
-            // mid columns per pass through a 2D LDS tile (6 -> two K=3
-            // groups; trailing 4/3/2 -> one uniform group). A trailing 5
-            // takes a full 6-column pass dipping one column below the
-            // low-tile boundary (the kernel only needs colLo >= 6); the
-            // ladder below then peels to 4-alignment as usual.
-            const int rem = (int)(i - (bitLenInt)tb);
-            const int nc = rem >= 5 ? 6 : rem;
-            if (nc >= 2 && (int)i - nc >= 6) {
-                HipProfScope prof("qft_mid_lds", stream);
-                if (basisPending_) {
-                    launchQftMidLdsBasis<R>(wStateAll(), maxQPower, (int)i - nc, nc, +1, false,
-                        basisPerm_, basisPhase_, stream);
-                } else {
-                    launchQftMidLds<R>(wState(), maxQPower, (int)i - nc, nc, +1, false, stream);
-                }
-                i -= (bitLenInt)nc;
-                continue;
-            }
-            // rem == 1: the plain fused kernels below handle it
-        }
-        if (fuseMax >= 5 && col >= 4u && maxQPower >= 64u) {
+        } else if (p.nCols == 5) {
             HipProfScope prof("qft_column5", stream);
-            const bitCapInt tPows[5] = { pow2(start + col - 4u), pow2(start + col - 3u),
-                pow2(start + col - 2u), pow2(start + col - 1u), pow2(start + col) };
+            const bitCapInt tPows[5] = { pow2(start + lo), pow2(start + lo + 1u),
+                pow2(start + lo + 2u), pow2(start + lo + 3u), pow2(start + lo + 4u) };
             launchQftColumnK<R>(wState(), maxQPower, start, col, 5, tPows, +1, false, stream);
-            i -= 5u;
-            continue;
-        }
-        if (fuseMax >= 4 && col >= 3u && maxQPower >= 32u) {
+        } else if (p.nCols == 4) {
             HipProfScope prof("qft_column4", stream);
-            const bitCapInt tPows[5] = { pow2(start + col - 3u), pow2(start + col - 2u),
-                pow2(start + col - 1u), pow2(start + col), 0u };
+            const bitCapInt tPows[5] = { pow2(start + lo), pow2(start + lo + 1u),
+                pow2(start + lo + 2u), pow2(start + lo + 3u), 0u };
             launchQftColumnK<R>(wState(), maxQPower, start, col, 4, tPows, +1, false, stream);
-            i -= 4u;
-            continue;
-        }
-        if (fuseMax >= 3 && col >= 2u && maxQPower >= 16u) {
+        } else if (p.nCols == 3) {
             // three columns per pass (8-amplitude orbits)
             HipProfScope prof("qft_column3", stream);
             launchQftColumn3<R>(wState(), maxQPower, start, col, pow2(start + col),
                 pow2(start + col - 1u), pow2(start + col - 2u), +1, false, stream);
-            i -= 3u;
-            continue;
-        }
-        if (fuseMax >= 2 && col >= 1u && maxQPower >= 8u) {
-            // two columns per pass
+        } else if (p.nCols == 2) {
             HipProfScope prof("qft_column2", stream);
             launchQftColumn2<R>(wState(), maxQPower, start, col, pow2(start + col),
                 pow2(start + col - 1u), +1, false, stream);
-            i -= 2u;
-            continue;
-        }
-        if (!col) {
+        } else if (!col) {
             this->H(start);
-            break;
+        } else {
+            HipProfScope prof("qft_column", stream);
+            launchQftColumn<R>(wState(), maxQPower, start, col, pow2(start + col), +1, false, stream);
         }
-        HipProfScope prof("qft_column", stream);
-        launchQftColumn<R>(wState(), maxQPower, start, col, pow2(start + col), +1, false, stream);
-        --i;
     }
 }
 
 template <typename R> void QEngineHIP<R>::IQFT(bitLenInt start, bitLenInt length, bool)
 {
+    // The forward plan walked backwards, lowest pass first, every pass the
+    // adjoint (pre-ramp, opposite sign) of the forward one: the exact
+    // adjoint schedule whatever the planner chose.
     if (!length) return;
     QA_HIP_CHECK(hipSetDevice(deviceId));
-    static const int fuseMax = []() {
-        if (const char* env = std::getenv("QRACK_GPU_QFT_FUSE2")) {
-            return std::atoi(env) != 0 ? 3 : 1;
-        }
-        if (const char* env = std::getenv("QRACK_GPU_QFT_FUSE")) return std::atoi(env);
-        return 4;
-    }();
-    static const bool ldsLow = []() {
-        if (const char* env = std::getenv("QRACK_GPU_QFT_LDS")) return std::atoi(env) != 0;
-        return true;
-    }();
-    static const bool ldsMid = []() {
-        if (sizeof(R) != 4) return false;
-        if (const char* env = std::getenv("QRACK_GPU_QFT_MIDLDS")) return std::atoi(env) != 0;
-        return true;
-    }();
+    const QftPlanOpts& opts = qftPlanOpts();
     const int tb = qaLdsTileBits<R>();
-    bitLenInt i = 0;
-    if (ldsLow && start == 0u && length > 0u && maxQPower >= (ONE_BCI << tb)) {
-        // the bottom K-aligned stretch of the ladder in ONE LDS pass; the
-        // few columns above it ride the ascending fusion below
-        const bitLenInt AK = (bitLenInt)qaLowLadderK<R>();
-        const bitLenInt L = (std::min<bitLenInt>(length, (bitLenInt)tb) / AK) * AK;
-        if (L >= AK) {
+    const std::vector<QftPass> plan =
+        qftPassPlan((int)length, (int)start, (int)qubitCount, (int)sizeof(R), opts);
+    for (auto it = plan.rbegin(); it != plan.rend(); ++it) {
+        const QftPass& p = *it;
+        const bitLenInt lo = (bitLenInt)p.colLo;
+        const bitLenInt col = (bitLenInt)(p.colLo + p.nCols - 1);
+        if (p.kind == QftPassKind::Low) {
             HipProfScope prof("qft_low_lds", stream);
             if (basisPending_) {
-                launchQftLowLdsBasis<R>(wStateAll(), maxQPower, tb, (int)L - 1, -1, true,
+                launchQftLowLdsBasis<R>(wStateAll(), maxQPower, tb, (int)col, -1, true,
                     basisPerm_, basisPhase_, stream);
             } else {
-                launchQftLowLds<R>(wState(), maxQPower, tb, (int)L - 1, -1, true, stream);
+                launchQftLowLds<R>(wState(), maxQPower, tb, (int)col, -1, true, stream);
             }
-            i = L;
-        }
-    }
-    while (i < length) {
-        if (ldsLow && ldsMid && start == 0u && i >= (bitLenInt)tb && i < length &&
-            maxQPower >= (ONE_BCI << tb)) {
-            const int rem = (int)(length - i);
-            const int nc = rem >= 6 ? 6 : (rem == 5 ? 4 : rem);
-            if (nc >= 2) {
-                HipProfScope prof("qft_mid_lds", stream);
-                if (basisPending_) {
-                    launchQftMidLdsBasis<R>(wStateAll(), maxQPower, (int)i, nc, -1, true,
-                        basisPerm_, basisPhase_, stream);
+        } else if (p.kind == QftPassKind::Mid) {
+            HipProfScope prof("qft_mid_lds", stream);
+            if (p.nCols >= QA_QFT_WIDE_MIN_COLS) {
+                if constexpr (sizeof(R) == 4) {
+                    const bool basis = basisPending_;
+                    cplx<R>* sv = basis ? wStateAll() : wState();
+                    launchQftMidWide(sv, maxQPower, opts.wideLowBits, p.colLo, p.nCols, -1, true,
+                        basis, basisPerm_, basisPhase_, stream);
                 } else {
-                    launchQftMidLds<R>(wState(), maxQPower, (int)i, nc, -1, true, stream);
+                    throw QrackError("IQFT: wide mid pass planned for a non-fp32 engine");
                 }
-                i += (bitLenInt)nc;
-                continue;
+            } else if (basisPending_) {
+                launchQftMidLdsBasis<R>(wStateAll(), maxQPower, p.colLo, p.nCols, -1, true,
+                    basisPerm_, basisPhase_, stream);
+            } else {
+                launchQftMidLds<R>(wState(), maxQPower, p.colLo, p.nCols, -1, true, stream);
             }
-        }
-        if (fuseMax >= 5 && (i + 4u) < length && maxQPower >= 64u) {
+        } else if (p.nCols == 5) {
             HipProfScope prof("qft_column5", stream);
-            const bitCapInt tPows[5] = { pow2(start + i), pow2(start + i + 1u),
-                pow2(start + i + 2u), pow2(start + i + 3u), pow2(start + i + 4u) };
-            launchQftColumnK<R>(
-                wState(), maxQPower, start, (bitLenInt)(i + 4u), 5, tPows, -1, true, stream);
-            i += 5u;
-            continue;
-        }
-        if (fuseMax >= 4 && (i + 3u) < length && maxQPower >= 32u) {
+            const bitCapInt tPows[5] = { pow2(start + lo), pow2(start + lo + 1u),
+                pow2(start + lo + 2u), pow2(start + lo + 3u), pow2(start + lo + 4u) };
+            launchQftColumnK<R>(wState(), maxQPower, start, col, 5, tPows, -1, true, stream);
+        } else if (p.nCols == 4) {
             HipProfScope prof("qft_column4", stream);
-            const bitCapInt tPows[5] = { pow2(start + i), pow2(start + i + 1u),
-                pow2(start + i + 2u), pow2(start + i + 3u), 0u };
-            launchQftColumnK<R>(
-                wState(), maxQPower, start, (bitLenInt)(i + 3u), 4, tPows, -1, true, stream);
-            i += 4u;
-            continue;
-        }
-        if (fuseMax >= 3 && (i + 2u) < length && maxQPower >= 16u) {
-            // triple (lo=i, mid=i+1, hi=i+2): exact adjoint of the forward
-            // triple (a lo column of 0 degenerates to the plain H inside)
+            const bitCapInt tPows[5] = { pow2(start + lo), pow2(start + lo + 1u),
+                pow2(start + lo + 2u), pow2(start + lo + 3u), 0u };
+            launchQftColumnK<R>(wState(), maxQPower, start, col, 4, tPows, -1, true, stream);
+        } else if (p.nCols == 3) {
+            // triple (lo, lo+1, lo+2): exact adjoint of the forward triple
+            // (a lo column of 0 degenerates to the plain H inside)
             HipProfScope prof("qft_column3", stream);
-            launchQftColumn3<R>(wState(), maxQPower, start, (bitLenInt)(i + 2u),
-                pow2(start + i + 2u), pow2(start + i + 1u), pow2(start + i), -1, true, stream);
-            i += 3u;
-            continue;
-        }
-        if (fuseMax >= 2 && (i + 1u) < length && maxQPower >= 8u) {
+            launchQftColumn3<R>(wState(), maxQPower, start, col, pow2(start + col),
+                pow2(start + col - 1u), pow2(start + lo), -1, true, stream);
+        } else if (p.nCols == 2) {
             HipProfScope prof("qft_column2", stream);
-            launchQftColumn2<R>(wState(), maxQPower, start, (bitLenInt)(i + 1u),
-                pow2(start + i + 1u), pow2(start + i), -1, true, stream);
-            i += 2u;
-            continue;
-        }
-        if (!i) {
+            launchQftColumn2<R>(wState(), maxQPower, start, col, pow2(start + col), pow2(start + lo),
+                -1, true, stream);
+        } else if (!col) {
             this->H(start);
-            ++i;
-            continue;
+        } else {
+            HipProfScope prof("qft_column", stream);
+            launchQftColumn<R>(wState(), maxQPower, start, col, pow2(start + col), -1, true, stream);
         }
-        HipProfScope prof("qft_column", stream);
-        launchQftColumn<R>(wState(), maxQPower, start, i, pow2(start + i), -1, true, stream);
-        ++i;
     }
 }
 

@@ -1,0 +1,159 @@
+// QFT pass planner: which kernels, over which columns, a start-0 QFT of
+// `length` qubits takes on the HIP engine. Pure host code, no HIP includes,
+// so the bindings expose it without a GPU. QEngineHIP<R>::QFT walks the
+// list top-down; IQFT walks it backwards with every pass adjointed, so the
+// inverse is always the exact mirror of the forward schedule.
+#pragma once
+
+#include <algorithm>
+#include <array>
+#include <climits>
+#include <vector>
+
+namespace qrack_amd {
+
+enum class QftPassKind {
+    Low, // low ladder: columns nCols-1..0 inside contiguous LDS tiles
+    Mid, // 2D LDS tile pass; nCols <= 6 on the 64-wide kernel, 8/9 on the wide one
+    Col  // nCols (1..5) fused register columns, one state pass; column 0 alone is an H
+};
+
+struct QftPass {
+    QftPassKind kind;
+    int colLo; // lowest column of the pass
+    int nCols; // columns colLo .. colLo+nCols-1
+};
+
+// mid-pass widths: on the 64-amplitude-run kernel, and on the wide-tile one
+constexpr int QA_QFT_MID_LOWBITS = 6;
+constexpr int QA_QFT_WIDE_MIN_COLS = 8;
+constexpr int QA_QFT_WIDE_MAX_COLS = 9;
+
+struct QftPlanOpts {
+    bool ldsLow = true;   // QRACK_GPU_QFT_LDS
+    bool ldsMid = true;   // QRACK_GPU_QFT_MIDLDS (fp32 only, whatever is asked)
+    int fuseMax = 4;      // QRACK_GPU_QFT_FUSE
+    int midMax = 9;       // QRACK_GPU_QFT_MIDMAX; <= 7 leaves only the 64-wide kernel
+    int wideLowBits = 4;  // contiguous-run bits of the wide kernel (colLo bound)
+};
+
+namespace qftplan {
+
+// register-column pass the fused kernels take with `i` columns left
+inline int fusedCols(int i, int width, int fuseMax)
+{
+    const int col = i - 1;
+    if (fuseMax >= 5 && col >= 4 && width >= 6) return 5;
+    if (fuseMax >= 4 && col >= 3 && width >= 5) return 4;
+    if (fuseMax >= 3 && col >= 2 && width >= 4) return 3;
+    if (fuseMax >= 2 && col >= 1 && width >= 3) return 2;
+    return 1;
+}
+
+// The six-columns-at-a-time schedule: mid passes of 6 (a trailing 5 takes
+// a full 6 dipping one column below the tile boundary), a trailing 4/3/2 as
+// one uniform group, then the K-aligned low ladder under peeled columns.
+inline std::vector<QftPass> greedy(int length, bool lds, bool mid, int tb, int AK, int width,
+    int fuseMax)
+{
+    std::vector<QftPass> plan;
+    int i = length;
+    while (i > 0) {
+        if (lds && i <= tb) {
+            const int r = i % AK;
+            if (!r) {
+                plan.push_back({ QftPassKind::Low, 0, i });
+                break;
+            }
+            if (i != r) {
+                plan.push_back({ QftPassKind::Col, i - r, r });
+                i -= r;
+                continue;
+            }
+        }
+        if (lds && mid && i > tb) {
+            const int rem = i - tb;
+            const int nc = rem >= 5 ? 6 : rem;
+            if (nc >= 2 && i - nc >= QA_QFT_MID_LOWBITS) {
+                plan.push_back({ QftPassKind::Mid, i - nc, nc });
+                i -= nc;
+                continue;
+            }
+        }
+        const int k = fusedCols(i, width, fuseMax);
+        plan.push_back({ QftPassKind::Col, i - k, k });
+        i -= k;
+    }
+    return plan;
+}
+
+} // namespace qftplan
+
+// Pass list, top column first, for a QFT over bits start..start+length-1 of a
+// `width`-qubit engine whose real type has `realBytes` bytes.
+//
+// With no wide width allowed (midMax < 8) this is the six-at-a-time
+// schedule above. Otherwise a search over
+//   - a low ladder of i columns (i <= tile bits, i a multiple of the ladder K),
+//   - a mid pass of 2/3/4/6 columns (colLo >= 6) or 8/9 columns (colLo >=
+//     wideLowBits) whose top column is above the low tile,
+//   - 1..fuseMax fused register columns
+// takes the fewest state passes; among equals the fewest wide passes, then
+// the fewest 8-column (K=4) ones. The six-at-a-time schedule is kept unless
+// the search is strictly better under that order.
+inline std::vector<QftPass> qftPassPlan(
+    int length, int start, int width, int realBytes, const QftPlanOpts& o = QftPlanOpts())
+{
+    const int tb = realBytes == 4 ? 12 : 11;
+    const int AK = realBytes == 4 ? 4 : 3;
+    const bool lds = o.ldsLow && start == 0 && width >= tb;
+    const bool mid = o.ldsMid && realBytes == 4;
+    std::vector<QftPass> base = qftplan::greedy(length, lds, mid, tb, AK, width, o.fuseMax);
+    const int wideMax = std::min(o.midMax, QA_QFT_WIDE_MAX_COLS);
+    if (!lds || !mid || wideMax < QA_QFT_WIDE_MIN_COLS || length <= tb) return base;
+
+    using Cost = std::array<int, 3>; // passes, wide passes, 8-column wide passes
+    const Cost inf{ INT_MAX, INT_MAX, INT_MAX };
+    std::vector<Cost> best(length + 1, inf);
+    std::vector<QftPass> step(length + 1, QftPass{ QftPassKind::Col, 0, 0 });
+    best[0] = Cost{ 0, 0, 0 };
+    auto consider = [&](int i, QftPass p, int rest, Cost add) {
+        if (best[rest] == inf) return;
+        const Cost c{ best[rest][0] + add[0], best[rest][1] + add[1], best[rest][2] + add[2] };
+        if (c < best[i]) {
+            best[i] = c;
+            step[i] = p;
+        }
+    };
+    const int narrow[4] = { 6, 4, 3, 2 };
+    for (int i = 1; i <= length; ++i) {
+        if (i <= tb && (i % AK) == 0) consider(i, { QftPassKind::Low, 0, i }, 0, { 1, 0, 0 });
+        if (i > tb) {
+            // among plans of equal cost the first found stays: wide on top
+            for (int nc = wideMax; nc >= QA_QFT_WIDE_MIN_COLS; --nc) {
+                if (i - nc >= o.wideLowBits) {
+                    consider(i, { QftPassKind::Mid, i - nc, nc }, i - nc, { 1, 1, nc == 8 ? 1 : 0 });
+                }
+            }
+            for (int nc : narrow) {
+                if (i - nc >= QA_QFT_MID_LOWBITS) {
+                    consider(i, { QftPassKind::Mid, i - nc, nc }, i - nc, { 1, 0, 0 });
+                }
+            }
+        }
+        const int kMax = std::min({ i, std::max(1, std::min(o.fuseMax, 5)), std::max(1, width - 1) });
+        for (int k = kMax; k >= 1; --k) {
+            consider(i, { QftPassKind::Col, i - k, k }, i - k, { 1, 0, 0 });
+        }
+    }
+    const Cost baseCost{ (int)base.size(), 0, 0 };
+    if (!(best[length] < baseCost)) return base;
+    std::vector<QftPass> plan;
+    for (int i = length; i > 0; i = step[i].colLo) {
+        plan.push_back(step[i]);
+        if (step[i].kind == QftPassKind::Low) break;
+    }
+    return plan;
+}
+
+} // namespace qrack_amd

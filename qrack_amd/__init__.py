@@ -23,6 +23,7 @@ from qrack_amd._qrack import (  # noqa: F401
     hip_device_count,
     profile_report,
     profile_reset,
+    qft_pass_plan,
     save_stabilizer_F,
     save_stabilizer_D,
     load_stabilizer_F,
