@@ -65,6 +65,16 @@ static inline int gridFor(bitCapInt n)
     return (int)b;
 }
 
+// one block per LDS tile, up to QA_MAX_BLOCKS and the QRACK_GPU_BLOCKS cap:
+// the LDS gate-batch kernels loop over the remaining tiles
+static inline int ldsGridFor(bitCapInt nTiles)
+{
+    bitCapInt b = std::min<bitCapInt>(nTiles, (bitCapInt)QA_MAX_BLOCKS);
+    const int cap = maxBlocks();
+    if (cap > 0 && b > (bitCapInt)cap) b = cap;
+    return (int)b;
+}
+
 // nontemporal (streaming) load/store option for the pure-stream kernels:
 // state-vector gate traffic has zero reuse, so bypassing L2/LLC can help
 typedef float nat_float4 __attribute__((ext_vector_type(4)));
@@ -3006,7 +3016,7 @@ template <typename R>
 void launchMtrx1qBatchLds(cplx<R>* sv, const BatchLdsArgs<R>& a, hipStream_t stream)
 {
     const bitCapInt nTiles = a.maxQPower >> qaLdsTileBits<R>();
-    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_MAX_BLOCKS);
+    const int grid = ldsGridFor(nTiles);
     hipLaunchKernelGGL((k_mtrx_batch_lds<R>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv, a);
 }
 
@@ -3055,7 +3065,7 @@ template <typename R>
 void launchMtrx2qBatchLds(cplx<R>* sv, const Batch2qLdsArgs<R>& a, hipStream_t stream)
 {
     const bitCapInt nTiles = a.maxQPower >> qaLdsTileBits<R>();
-    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_MAX_BLOCKS);
+    const int grid = ldsGridFor(nTiles);
     hipLaunchKernelGGL((k_mtrx2q_batch_lds<R>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv, a);
 }
 

@@ -155,6 +155,7 @@ template <typename R> QEngineHIP<R>::~QEngineHIP()
     if (dState_) freeDev(dState_, maxQPower);
     releaseScratch();
     releaseTileSums();
+    releaseAux();
     if (dPartials) hipFree(dPartials);
     if (dIdx) hipFree(dIdx);
     hipStreamDestroy(stream);
@@ -221,6 +222,33 @@ template <typename R> void QEngineHIP<R>::setStateBuffer(cplx<R>* buf)
     releaseTileSums();
 }
 
+template <typename R> void QEngineHIP<R>::releaseAux()
+{
+    if (dAux_) hipFree(dAux_);
+    dAux_ = nullptr;
+    auxBytes_ = 0;
+}
+
+// The tables used to go into a fresh hipMallocAsync block per call, freed with
+// hipFreeAsync after the kernel. From the second call on one engine the kernel
+// could then read something other than the table just copied there: the
+// multiplexer returned an all-zero state or applied matrix 0 everywhere, and
+// the indexed ALU ops lost norm. A buffer the engine keeps has no such window.
+// Callers wait for the stream before they refill hAux_, so that neither the
+// last kernel still reads dAux_ nor the last copy still reads hAux_.
+template <typename R> unsigned char* QEngineHIP<R>::uploadAux(size_t bytes)
+{
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    if (bytes > auxBytes_) {
+        QA_HIP_CHECK(hipStreamSynchronize(stream));
+        releaseAux();
+        QA_HIP_CHECK(hipMalloc(&dAux_, bytes));
+        auxBytes_ = bytes;
+    }
+    QA_HIP_CHECK(hipMemcpyAsync(dAux_, hAux_.data(), bytes, hipMemcpyHostToDevice, stream));
+    return dAux_;
+}
+
 template <typename R> void QEngineHIP<R>::releaseTileSums()
 {
     if (dTileSums_) hipFree(dTileSums_);
@@ -283,6 +311,7 @@ template <typename R> void QEngineHIP<R>::SetDevice(int64_t devId)
     GetQuantumState(host.data());
     releaseScratch();
     releaseTileSums();
+    releaseAux();
     freeDev(dState_, maxQPower);
     hipStreamDestroy(stream);
     hipFree(dPartials);
@@ -863,20 +892,18 @@ void QEngineHIP<R>::UniformlyControlledSingleBit(
     }
     QA_HIP_CHECK(hipSetDevice(deviceId));
     const bitCapInt nMtrx = pow2((bitLenInt)controls.size());
-    std::vector<bitCapInt> ctrlPowers(controls.size());
-    for (size_t i = 0; i < controls.size(); ++i) ctrlPowers[i] = pow2(controls[i]);
-    bitCapInt* dPowers = nullptr;
-    cplx<R>* dMtrxs = nullptr;
-    QA_HIP_CHECK(hipMallocAsync(&dPowers, sizeof(bitCapInt) * controls.size(), stream));
-    QA_HIP_CHECK(hipMallocAsync(&dMtrxs, sizeof(cplx<R>) * 4 * nMtrx, stream));
-    QA_HIP_CHECK(hipMemcpyAsync(dPowers, ctrlPowers.data(), sizeof(bitCapInt) * controls.size(),
-        hipMemcpyHostToDevice, stream));
-    QA_HIP_CHECK(
-        hipMemcpyAsync(dMtrxs, mtrxs, sizeof(cplx<R>) * 4 * nMtrx, hipMemcpyHostToDevice, stream));
-    launchUniformlyControlled<R>(wState(), maxQPower >> 1u, pow2(target), dPowers,
-        (int)controls.size(), dMtrxs, stream);
-    QA_HIP_CHECK(hipFreeAsync(dPowers, stream));
-    QA_HIP_CHECK(hipFreeAsync(dMtrxs, stream));
+    // control powers first, then the matrices, in one upload
+    const size_t powBytes = (sizeof(bitCapInt) * controls.size() + 15u) & ~(size_t)15u;
+    const size_t mtrxBytes = sizeof(cplx<R>) * 4 * nMtrx;
+    QA_HIP_CHECK(hipStreamSynchronize(stream)); // hAux_ and dAux_ are free again
+    hAux_.assign(powBytes + mtrxBytes, 0);
+    bitCapInt* hPowers = reinterpret_cast<bitCapInt*>(hAux_.data());
+    for (size_t i = 0; i < controls.size(); ++i) hPowers[i] = pow2(controls[i]);
+    std::memcpy(hAux_.data() + powBytes, mtrxs, mtrxBytes);
+    unsigned char* dAux = uploadAux(powBytes + mtrxBytes);
+    launchUniformlyControlled<R>(wState(), maxQPower >> 1u, pow2(target),
+        reinterpret_cast<const bitCapInt*>(dAux), (int)controls.size(),
+        reinterpret_cast<const cplx<R>*>(dAux + powBytes), stream);
 }
 
 template <typename R>
@@ -2055,14 +2082,11 @@ void QEngineHIP<R>::CPOWModNOut(bitCapInt base, bitCapInt modN, bitLenInt inStar
     permuteOp(a, true, true);
 }
 
-template <typename R>
-static unsigned char* uploadTable(
-    const unsigned char* values, size_t bytes, int deviceId, hipStream_t stream)
+template <typename R> unsigned char* QEngineHIP<R>::uploadTable(const unsigned char* values, size_t bytes)
 {
-    unsigned char* dTable = nullptr;
-    QA_HIP_CHECK(hipMallocAsync(&dTable, bytes, stream));
-    QA_HIP_CHECK(hipMemcpyAsync(dTable, values, bytes, hipMemcpyHostToDevice, stream));
-    return dTable;
+    QA_HIP_CHECK(hipStreamSynchronize(stream)); // hAux_ and dAux_ are free again
+    hAux_.assign(values, values + bytes);
+    return uploadAux(bytes);
 }
 
 template <typename R>
@@ -2072,7 +2096,7 @@ bitCapInt QEngineHIP<R>::IndexedLDA(bitLenInt indexStart, bitLenInt indexLength,
     if (resetValue) {
         const int bytes = (int)((valueLength + 7u) / 8u);
         unsigned char* dTable =
-            uploadTable<R>(values, ((size_t)1 << indexLength) * bytes, deviceId, stream);
+            uploadTable(values, ((size_t)1 << indexLength) * bytes);
         PermArgs a{};
         a.op = (int)PermOp::LDA;
         a.start = indexStart;
@@ -2086,7 +2110,6 @@ bitCapInt QEngineHIP<R>::IndexedLDA(bitLenInt indexStart, bitLenInt indexLength,
         fillSkips(a, powers);
         a.maxI = maxQPower >> valueLength;
         permuteOp(a, true, false);
-        QA_HIP_CHECK(hipFreeAsync(dTable, stream));
     }
     std::vector<bitLenInt> bits;
     for (bitLenInt i = 0; i < valueLength; ++i) bits.push_back(valueStart + i);
@@ -2105,7 +2128,7 @@ bitCapInt QEngineHIP<R>::IndexedADC(bitLenInt indexStart, bitLenInt indexLength,
     }
     const int bytes = (int)((valueLength + 7u) / 8u);
     unsigned char* dTable =
-        uploadTable<R>(values, ((size_t)1 << indexLength) * bytes, deviceId, stream);
+        uploadTable(values, ((size_t)1 << indexLength) * bytes);
     PermArgs a{};
     a.op = (int)PermOp::ADC;
     a.start = indexStart;
@@ -2119,7 +2142,6 @@ bitCapInt QEngineHIP<R>::IndexedADC(bitLenInt indexStart, bitLenInt indexLength,
     fillSkips(a, { a.carryMask });
     a.maxI = maxQPower >> 1u;
     permuteOp(a, true, false);
-    QA_HIP_CHECK(hipFreeAsync(dTable, stream));
     std::vector<bitLenInt> bits;
     for (bitLenInt i = 0; i < valueLength; ++i) bits.push_back(valueStart + i);
     return (bitCapInt)(this->ExpectationBitsAll(bits) + 0.5);
@@ -2138,7 +2160,7 @@ bitCapInt QEngineHIP<R>::IndexedSBC(bitLenInt indexStart, bitLenInt indexLength,
     }
     const int bytes = (int)((valueLength + 7u) / 8u);
     unsigned char* dTable =
-        uploadTable<R>(values, ((size_t)1 << indexLength) * bytes, deviceId, stream);
+        uploadTable(values, ((size_t)1 << indexLength) * bytes);
     PermArgs a{};
     a.op = (int)PermOp::SBC;
     a.start = indexStart;
@@ -2152,7 +2174,6 @@ bitCapInt QEngineHIP<R>::IndexedSBC(bitLenInt indexStart, bitLenInt indexLength,
     fillSkips(a, { a.carryMask });
     a.maxI = maxQPower >> 1u;
     permuteOp(a, true, false);
-    QA_HIP_CHECK(hipFreeAsync(dTable, stream));
     std::vector<bitLenInt> bits;
     for (bitLenInt i = 0; i < valueLength; ++i) bits.push_back(valueStart + i);
     return (bitCapInt)(this->ExpectationBitsAll(bits) + 0.5);
@@ -2162,7 +2183,7 @@ template <typename R>
 void QEngineHIP<R>::Hash(bitLenInt start, bitLenInt length, const unsigned char* values)
 {
     const int bytes = (int)((length + 7u) / 8u);
-    unsigned char* dTable = uploadTable<R>(values, ((size_t)1 << length) * bytes, deviceId, stream);
+    unsigned char* dTable = uploadTable(values, ((size_t)1 << length) * bytes);
     PermArgs a{};
     a.op = (int)PermOp::HASH;
     a.maxI = maxQPower;
@@ -2171,7 +2192,6 @@ void QEngineHIP<R>::Hash(bitLenInt start, bitLenInt length, const unsigned char*
     a.table = dTable;
     a.tableBytes = bytes;
     permuteOp(a, false, false);
-    QA_HIP_CHECK(hipFreeAsync(dTable, stream));
 }
 
 template <typename R> void QEngineHIP<R>::ROL(bitLenInt shift, bitLenInt start, bitLenInt length)

@@ -88,6 +88,15 @@ protected:
     double* dPartials = nullptr; // reduce partials (QA-reduce grid max + argmax idx)
     bitCapInt* dIdx = nullptr;
     std::vector<double> hPartials;
+    // host tables that a kernel reads (multiplexer matrices and control powers,
+    // ALU lookup tables): one engine-owned device buffer, grown on demand
+    unsigned char* dAux_ = nullptr;
+    size_t auxBytes_ = 0;
+    std::vector<unsigned char> hAux_;
+    // stage `bytes` of hAux_ into dAux_ in stream order; returns dAux_
+    unsigned char* uploadAux(size_t bytes);
+    unsigned char* uploadTable(const unsigned char* values, size_t bytes);
+    void releaseAux();
 
 public:
     QEngineHIP(bitLenInt qBitCount, bitCapInt initState = 0u, RngPtr rgp = nullptr,

@@ -54,6 +54,20 @@ def test_controlled_op_moves_a_basis_state(precision):
     assert abs(sv[79]) == 1.0
 
 
+@pytest.mark.parametrize("precision", ["fp32", "fp64"])
+def test_table_ops_repeated_on_one_engine(precision):
+    """The indexed ops and hash upload their table for every call, the way
+    the multiplexer uploads its matrices; there, calls after the first on
+    one engine intermittently read zeros in place of the upload. Every other
+    test here makes a new engine per case, so: three rounds of the table
+    cases on one engine."""
+    cases = [c for c in ac.BASE_CASES if c.op in ("indexed_lda", "indexed_adc", "hash") and not c.rescaled]
+    q = make(10, precision)
+    for _ in range(3):
+        for case in cases:
+            ac.run_case(q, case, precision)
+
+
 _CHILD = """
 import sys
 sys.path.insert(0, sys.argv[1])
