@@ -30,6 +30,26 @@ template <typename R> static const char* dtypeName();
 template <> const char* dtypeName<float>() { return "complex64"; }
 template <> const char* dtypeName<double>() { return "complex128"; }
 
+// (coeff, [qubits], [paulis]) tuples -> PauliTerm list; `what` names the caller
+static std::vector<PauliTerm> pauliTermsFromTuples(
+    const std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>>& terms,
+    const char* what)
+{
+    std::vector<PauliTerm> ts;
+    ts.reserve(terms.size());
+    for (const auto& t : terms) {
+        PauliTerm pt;
+        pt.coeff = std::get<0>(t);
+        pt.bits = std::get<1>(t);
+        for (int p : std::get<2>(t)) {
+            if (p < 0 || p > 3) throw QrackError(std::string(what) + ": bad Pauli code");
+            pt.paulis.push_back((Pauli)p);
+        }
+        ts.push_back(std::move(pt));
+    }
+    return ts;
+}
+
 template <typename R> static void bindQInterface(py::module_& m, const char* name)
 {
     using QI = QInterface<R>;
@@ -429,6 +449,26 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
             },
             py::arg("terms"),
             "sum_t coeff_t <P_t> for terms (coeff, [qubits], [paulis]); Pauli codes 0=I 1=X 2=Z 3=Y")
+        .def("pauli_rotation",
+            [](QI& q, std::vector<bitLenInt> bits, std::vector<int> paulis, double theta) {
+                std::vector<Pauli> ps;
+                for (int p : paulis) {
+                    if (p < 0 || p > 3) throw QrackError("pauli_rotation: bad Pauli code");
+                    ps.push_back((Pauli)p);
+                }
+                q.PauliRotation(bits, ps, theta);
+            },
+            py::arg("qubits"), py::arg("paulis"), py::arg("theta"),
+            "exp(-i theta P), global phase included; a lone Z is RZ(2 theta). "
+            "Pauli codes 0=I 1=X 2=Z 3=Y")
+        .def("evolve_pauli_sum",
+            [](QI& q, std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms,
+                double time, int steps, int order) {
+                q.EvolvePauliSum(pauliTermsFromTuples(terms, "evolve_pauli_sum"), time, steps, order);
+            },
+            py::arg("terms"), py::arg("time"), py::arg("steps") = 1, py::arg("order") = 1,
+            "exp(-i time H) for H = sum of (coeff, [qubits], [paulis]) terms as a first- or "
+            "second-order product formula of `steps` steps")
         .def("prob_bits_all",
             [](QI& q, std::vector<bitLenInt> bits) {
                 py::array_t<double> out((py::ssize_t)pow2((bitLenInt)bits.size()));
@@ -850,6 +890,26 @@ PYBIND11_MODULE(_qrack, m)
     m.def("hip_device_count", &HipDeviceCount);
     // the HIP engine's QFT schedule for a start-0 register, top pass first,
     // as (kind, colLo, nCols) with kind "low" | "mid" | "col"; needs no GPU
+    m.def(
+        "pauli_evolve_plan",
+        [](std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms, int n,
+            double time, int steps, int order) {
+            if (n < 1 || n > 64) throw std::invalid_argument("pauli_evolve_plan: need 1 <= n <= 64");
+            const PauliCanonSum c = canonicalizePauliSum(
+                pauliTermsFromTuples(terms, "pauli_evolve_plan"), (bitLenInt)n, "pauli_evolve_plan");
+            py::list out;
+            for (const PauliEvolvePass& p : pauliEvolvePlan(c, time, steps, order).passes) {
+                py::list segs;
+                for (const PauliEvolveSeg& sg : p.segs) {
+                    segs.append(py::make_tuple(sg.im ? "im" : "re", sg.tau));
+                }
+                out.append(py::make_tuple(p.group, c.groups[p.group].x, segs));
+            }
+            return out;
+        },
+        py::arg("terms"), py::arg("n"), py::arg("time"), py::arg("steps") = 1, py::arg("order") = 1,
+        "passes the dense engines walk for evolve_pauli_sum: (group index, X/Y mask, "
+        "[(parity set, tau), ...]) each");
     m.def(
         "qft_pass_plan",
         [](int length, int width, const std::string& precision, int midmax) {

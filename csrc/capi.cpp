@@ -556,6 +556,42 @@ double qrack_expectation_pauli_sum(quid sid, uint64_t nTerms, const double* coef
     });
 }
 
+void qrack_pauli_rotation(
+    quid sid, const int* paulis, const uint64_t* qs, uint64_t n, double theta)
+{
+    guarded(sid, [&](SimSlot& s) {
+        std::vector<bitLenInt> bits;
+        std::vector<Pauli> ps;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (paulis[i] < 0 || paulis[i] > 3)
+                throw QrackError("qrack_pauli_rotation: bad Pauli code");
+            bits.push_back((bitLenInt)qs[i]);
+            ps.push_back((Pauli)paulis[i]);
+        }
+        FOR_SIM(s, q.PauliRotation(bits, ps, theta));
+    });
+}
+
+void qrack_evolve_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, double time, int steps,
+    int order)
+{
+    guarded(sid, [&](SimSlot& s) {
+        std::vector<PauliTerm> terms(nTerms);
+        uint64_t at = 0;
+        for (uint64_t t = 0; t < nTerms; ++t) {
+            terms[t].coeff = coeffs[t];
+            for (uint64_t i = 0; i < termLens[t]; ++i, ++at) {
+                if (paulis[at] < 0 || paulis[at] > 3)
+                    throw QrackError("qrack_evolve_pauli_sum: bad Pauli code");
+                terms[t].bits.push_back((bitLenInt)qs[at]);
+                terms[t].paulis.push_back((Pauli)paulis[at]);
+            }
+        }
+        FOR_SIM(s, q.EvolvePauliSum(terms, time, steps, order));
+    });
+}
+
 void qrack_qft(quid sid, uint64_t start, uint64_t length)
 {
     guarded(sid, [&](SimSlot& s) { FOR_SIM(s, q.QFT((bitLenInt)start, (bitLenInt)length)); });

@@ -3418,8 +3418,8 @@ __device__ __forceinline__ void blockSumStore(double s, double* dst)
 }
 
 // weights of index i (even when TWO) and, when TWO, of i + 1
-template <bool TWO>
-__device__ __forceinline__ void pauliWeights(const PauliArgs& a, int first, int last, bitCapInt i,
+template <bool TWO, typename ARGS>
+__device__ __forceinline__ void pauliWeights(const ARGS& a, int first, int last, bitCapInt i,
     double& w0, double& w1)
 {
     w0 = 0;
@@ -3548,6 +3548,233 @@ void launchPauliGroup(const cplx<R>* sv, const PauliArgs& a, double* partialsDev
         k_pauli_finish, dim3(1), dim3(QA_BLOCK), 0, stream, partialsDev, grid, resultDev);
 }
 
+// ---- Pauli-sum evolution ---------------------------------------------------------
+//
+// exp(-i tau sum_t w_t P_t) for terms that share x, applied in place: the
+// per-pair algebra is in qengine.hpp (pauliEvolvePlan). Addressing is that of
+// k_pauli_group, so every amplitude is loaded once and stored once by exactly
+// one thread; where the partner vector's halves were swapped on load (fp32,
+// bit 0 of x set) they are swapped back before the store.
+
+// c + i s = e^{i angle} for segment k (its terms start at `first`) at index i,
+// and at i + 1 when TWO. SINGLE: the segment is one term, |angle| is constant
+// and the host's cos / sin are used, so only sin's sign depends on i. Otherwise
+// the angle is summed in double and sincos is the accurate double one: the
+// native fast sincos is off by ~10 eps (ARCHITECTURE.md, cphase_pairs).
+template <bool SINGLE, bool TWO, typename R>
+__device__ __forceinline__ void pauliEvolveCS(const PauliEvolveArgs& a, int k, int first, bitCapInt i,
+    R& c0, R& s0, R& c1, R& s1)
+{
+    if constexpr (SINGLE) {
+        const bitCapInt z = a.z[first];
+        const unsigned p0 = __popcll(i & z) & 1u;
+        const R c = (R)a.segCos[k];
+        const R s = (R)a.segSin[k];
+        c0 = c;
+        s0 = p0 ? -s : s;
+        if (TWO) {
+            c1 = c;
+            s1 = (p0 ^ (unsigned)(z & 1u)) ? -s : s;
+        }
+    } else {
+        double w0, w1, sd, cd;
+        pauliWeights<TWO>(a, first, a.segEnd[k], i, w0, w1);
+        sincos(w0, &sd, &cd);
+        c0 = (R)cd;
+        s0 = (R)sd;
+        if (TWO) {
+            sincos(w1, &sd, &cd);
+            c1 = (R)cd;
+            s1 = (R)sd;
+        }
+    }
+}
+
+// re set: (a, b) <- (c a - i s b, c b - i s a); im set: (a, b) <- (c a - s b, c b + s a)
+template <typename R>
+__device__ __forceinline__ void pauliEvolveRot(bool im, R c, R s, R& ar, R& ai, R& br, R& bi)
+{
+    const R par = ar, pai = ai, pbr = br, pbi = bi;
+    if (im) {
+        ar = c * par - s * pbr;
+        ai = c * pai - s * pbi;
+        br = c * pbr + s * par;
+        bi = c * pbi + s * pai;
+    } else {
+        ar = c * par + s * pbi;
+        ai = c * pai - s * pbr;
+        br = c * pbr + s * pai;
+        bi = c * pbi - s * par;
+    }
+}
+
+template <typename R> __device__ __forceinline__ void pauliEvolveScale(R pr, R pi, R& re, R& im)
+{
+    const R t = pr * re - pi * im;
+    im = pr * im + pi * re;
+    re = t;
+}
+
+// MODE as in k_pauli_group: 0 = one pair per item (fp64); 1 = two pairs per
+// item (fp32, x != 1); 2 = fp32, x == 1 (the pair is one vector)
+template <typename R, int MODE, bool SINGLE, bool NT>
+__global__ void k_pauli_evolve(cplx<R>* sv, PauliEvolveArgs a, bitCapInt nItems, bitCapInt topPow)
+{
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    const R pr = (R)a.phaseRe, pi = (R)a.phaseIm;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        R c0, s0, c1, s1;
+        if constexpr (MODE == 0) {
+            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
+            double2* p = reinterpret_cast<double2*>(sv);
+            double2 A = p[i];
+            double2 B = p[i ^ a.x];
+            int first = 0;
+            for (int k = 0; k < a.nSeg; ++k) {
+                pauliEvolveCS<SINGLE, false, double>(a, k, first, i, c0, s0, c1, s1);
+                pauliEvolveRot<double>(a.segIm[k] != 0, c0, s0, A.x, A.y, B.x, B.y);
+                first = a.segEnd[k];
+            }
+            if (a.hasPhase) {
+                pauliEvolveScale<double>(pr, pi, A.x, A.y);
+                pauliEvolveScale<double>(pr, pi, B.x, B.y);
+            }
+            p[i] = A;
+            p[i ^ a.x] = B;
+        } else if constexpr (MODE == 1) {
+            const bitCapInt j = v << 1u;
+            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
+            float4* p = reinterpret_cast<float4*>(sv);
+            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
+            float4 A = ld4<NT>(p + ia);
+            float4 B = ld4<NT>(p + ib);
+            const bool swapped = (a.x & 1u) != 0;
+            if (swapped) B = make_float4(B.z, B.w, B.x, B.y);
+            int first = 0;
+            for (int k = 0; k < a.nSeg; ++k) {
+                pauliEvolveCS<SINGLE, true, float>(a, k, first, i, c0, s0, c1, s1);
+                const bool im = a.segIm[k] != 0;
+                pauliEvolveRot<float>(im, c0, s0, A.x, A.y, B.x, B.y);
+                pauliEvolveRot<float>(im, c1, s1, A.z, A.w, B.z, B.w);
+                first = a.segEnd[k];
+            }
+            if (a.hasPhase) {
+                pauliEvolveScale<float>(pr, pi, A.x, A.y);
+                pauliEvolveScale<float>(pr, pi, A.z, A.w);
+                pauliEvolveScale<float>(pr, pi, B.x, B.y);
+                pauliEvolveScale<float>(pr, pi, B.z, B.w);
+            }
+            if (swapped) B = make_float4(B.z, B.w, B.x, B.y);
+            st4<NT>(p + ia, A);
+            st4<NT>(p + ib, B);
+        } else {
+            float4* p = reinterpret_cast<float4*>(sv);
+            const bitCapInt i = v << 1u;
+            float4 A = ld4<NT>(p + v);
+            int first = 0;
+            for (int k = 0; k < a.nSeg; ++k) {
+                pauliEvolveCS<SINGLE, false, float>(a, k, first, i, c0, s0, c1, s1);
+                pauliEvolveRot<float>(a.segIm[k] != 0, c0, s0, A.x, A.y, A.z, A.w);
+                first = a.segEnd[k];
+            }
+            if (a.hasPhase) {
+                pauliEvolveScale<float>(pr, pi, A.x, A.y);
+                pauliEvolveScale<float>(pr, pi, A.z, A.w);
+            }
+            st4<NT>(p + v, A);
+        }
+    }
+}
+
+// x == 0: psi[i] *= e^{-i angle(i)}, angle(i) the signed sum of the one segment
+template <typename R, bool SINGLE, bool NT>
+__global__ void k_pauli_evolve_diag(cplx<R>* sv, PauliEvolveArgs a, bitCapInt nItems)
+{
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    const R pr = (R)a.phaseRe, pi = (R)a.phaseIm;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        R c0, s0, c1, s1;
+        if constexpr (sizeof(R) == 4) {
+            float4* p = reinterpret_cast<float4*>(sv);
+            float4 A = ld4<NT>(p + v);
+            pauliEvolveCS<SINGLE, true, float>(a, 0, 0, v << 1u, c0, s0, c1, s1);
+            pauliEvolveScale<float>(c0, -s0, A.x, A.y);
+            pauliEvolveScale<float>(c1, -s1, A.z, A.w);
+            if (a.hasPhase) {
+                pauliEvolveScale<float>(pr, pi, A.x, A.y);
+                pauliEvolveScale<float>(pr, pi, A.z, A.w);
+            }
+            st4<NT>(p + v, A);
+        } else {
+            double2* p = reinterpret_cast<double2*>(sv);
+            double2 A = p[v];
+            pauliEvolveCS<SINGLE, false, double>(a, 0, 0, v, c0, s0, c1, s1);
+            pauliEvolveScale<double>(c0, -s0, A.x, A.y);
+            if (a.hasPhase) pauliEvolveScale<double>(pr, pi, A.x, A.y);
+            p[v] = A;
+        }
+    }
+}
+
+// pick the SINGLE / NT instantiation of one addressing mode; MODE < 0 is the
+// diagonal kernel
+template <typename R, int MODE>
+static void launchPauliEvolveMode(cplx<R>* sv, const PauliEvolveArgs& a, bitCapInt nItems,
+    bitCapInt topPow, bool single, hipStream_t stream)
+{
+    const dim3 g(gridFor(nItems)), b(QA_BLOCK);
+    // nontemporal access exists for the float4 streams only
+    const bool nt = (sizeof(R) == 4) && useNontemporal();
+#define QA_PE_LAUNCH(SINGLE, NT)                                                                    \
+    do {                                                                                            \
+        if constexpr (MODE < 0) {                                                                   \
+            hipLaunchKernelGGL((k_pauli_evolve_diag<R, SINGLE, NT>), g, b, 0, stream, sv, a, nItems); \
+        } else {                                                                                    \
+            hipLaunchKernelGGL(                                                                     \
+                (k_pauli_evolve<R, MODE, SINGLE, NT>), g, b, 0, stream, sv, a, nItems, topPow);     \
+        }                                                                                           \
+    } while (0)
+    if constexpr (sizeof(R) == 4) {
+        if (single) {
+            if (nt) QA_PE_LAUNCH(true, true);
+            else QA_PE_LAUNCH(true, false);
+        } else {
+            if (nt) QA_PE_LAUNCH(false, true);
+            else QA_PE_LAUNCH(false, false);
+        }
+    } else {
+        if (single) QA_PE_LAUNCH(true, false);
+        else QA_PE_LAUNCH(false, false);
+    }
+#undef QA_PE_LAUNCH
+}
+
+template <typename R>
+void launchPauliEvolve(cplx<R>* sv, const PauliEvolveArgs& a, hipStream_t stream)
+{
+    // the transcendental-free kernel needs every segment to hold one term
+    bool single = a.nSeg > 0;
+    for (int k = 0, first = 0; k < a.nSeg; first = a.segEnd[k++]) {
+        if (a.segEnd[k] - first != 1) single = false;
+    }
+    // an item is one 16-byte access per stream: two amplitudes in fp32, one in fp64
+    if (!a.x) {
+        launchPauliEvolveMode<R, -1>(
+            sv, a, (sizeof(R) == 4) ? (a.nAmps >> 1u) : a.nAmps, 0u, single, stream);
+        return;
+    }
+    const bitCapInt topPow = ONE_BCI << (63 - __builtin_clzll(a.x));
+    if constexpr (sizeof(R) == 4) {
+        if (a.x == 1u) {
+            launchPauliEvolveMode<R, 2>(sv, a, a.nAmps >> 1u, topPow, single, stream);
+        } else {
+            launchPauliEvolveMode<R, 1>(sv, a, a.nAmps >> 2u, topPow, single, stream);
+        }
+    } else {
+        launchPauliEvolveMode<R, 0>(sv, a, a.nAmps >> 1u, topPow, single, stream);
+    }
+}
+
 // ---- explicit instantiations ---------------------------------------------------
 
 #define QA_INSTANTIATE(R)                                                                           \
@@ -3559,6 +3786,7 @@ void launchPauliGroup(const cplx<R>* sv, const PauliArgs& a, double* partialsDev
     template int launchReduce<R>(const cplx<R>*, const ReduceArgs&, int, double*, hipStream_t);     \
     template int launchArgMax<R>(const cplx<R>*, bitCapInt, double*, bitCapInt*, hipStream_t);      \
     template void launchPauliGroup<R>(const cplx<R>*, const PauliArgs&, double*, double*, hipStream_t); \
+    template void launchPauliEvolve<R>(cplx<R>*, const PauliEvolveArgs&, hipStream_t);              \
     template void launchNormalize<R>(cplx<R>*, bitCapInt, cplx<R>, R, hipStream_t);                 \
     template void launchApplyM<R>(cplx<R>*, bitCapInt, bitCapInt, bitCapInt, cplx<R>, hipStream_t); \
     template void launchApplyParity<R>(cplx<R>*, bitCapInt, bitCapInt, bool, cplx<R>, hipStream_t); \

@@ -110,7 +110,37 @@ struct PauliArgs {
     double w[QA_PAULI_MAX_TERMS];
 };
 
+// One launch of the in-place Pauli-evolution pass on the pairs (i, i^x): up to
+// QA_PAULI_EVOLVE_MAX_SEGS segments, each a run of terms of one parity set
+// (entries [segEnd[k-1], segEnd[k]) of z / w). w holds tau * weight, formed
+// in double on the host, so a pair's rotation angle in a segment is the signed
+// sum of that segment's w. A launch whose segments all hold ONE term takes the
+// transcendental-free kernel: |angle| is constant, the host leaves
+// cos / sin of w[k] in segCos / segSin and the kernel only picks sin's sign
+// from the parity. phase (when hasPhase) is a scalar every amplitude is
+// multiplied by last. Like PauliArgs the table rides in the kernarg segment.
+constexpr int QA_PAULI_EVOLVE_MAX_SEGS = 4;
+
+struct PauliEvolveArgs {
+    bitCapInt x;     // X/Y mask; 0 selects the diagonal kernel (one re segment)
+    bitCapInt nAmps; // 2^qubits
+    int nSeg;
+    int hasPhase;
+    int segEnd[QA_PAULI_EVOLVE_MAX_SEGS];
+    int segIm[QA_PAULI_EVOLVE_MAX_SEGS]; // 0: re-set rotation, 1: im-set rotation
+    double segCos[QA_PAULI_EVOLVE_MAX_SEGS];
+    double segSin[QA_PAULI_EVOLVE_MAX_SEGS];
+    double phaseRe, phaseIm;
+    bitCapInt z[QA_PAULI_MAX_TERMS];
+    double w[QA_PAULI_MAX_TERMS];
+};
+
 // ---- launches (all asynchronous on `stream`) -------------------------------
+
+// One read-and-write pass: every amplitude is loaded once and stored once, by
+// exactly one thread.
+template <typename R>
+void launchPauliEvolve(cplx<R>* sv, const PauliEvolveArgs& a, hipStream_t stream);
 
 // sum_t w_t <psi|P_t|psi> for one group: stage 1 leaves per-block partials in
 // partialsDev (QA_REDUCE_MAX_BLOCKS doubles), stage 2 folds them in a fixed

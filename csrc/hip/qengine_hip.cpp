@@ -1297,6 +1297,87 @@ template <typename R> double QEngineHIP<R>::ExpectationPauliSum(const std::vecto
     return c.identity + pauliGroupsSum(c.groups);
 }
 
+// ---- Pauli rotations and Pauli-sum evolution ---------------------------------
+
+template <typename R>
+void QEngineHIP<R>::pauliEvolveRun(const PauliCanonSum& c, const PauliEvolvePlan& plan)
+{
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    cplx<R>* sv = wState();
+    // the identity phase rides on the first launch, or is one scalar multiply
+    bool phasePending = plan.phase != 0;
+    auto fresh = [&](bitCapInt x) {
+        PauliEvolveArgs a{};
+        a.x = x;
+        a.nAmps = maxQPower;
+        if (phasePending) {
+            a.hasPhase = 1;
+            a.phaseRe = std::cos(plan.phase);
+            a.phaseIm = -std::sin(plan.phase);
+            phasePending = false;
+        }
+        return a;
+    };
+    for (const PauliEvolvePass& pass : plan.passes) {
+        const PauliEvolveFlat f = pauliEvolveFlatten(c, pass);
+        const bitCapInt x = c.groups[pass.group].x;
+        HipProfScope prof("pauli_evolve", stream);
+        // A launch takes QA_PAULI_MAX_TERMS entries in QA_PAULI_EVOLVE_MAX_SEGS
+        // segments (one for the diagonal kernel). A longer segment continues
+        // in the next launch: its set commutes, so the split is exact.
+        const int maxSegs = x ? QA_PAULI_EVOLVE_MAX_SEGS : 1;
+        PauliEvolveArgs a = fresh(x);
+        int n = 0;
+        size_t t = 0;
+        for (size_t k = 0; k < f.segEnd.size(); ++k) {
+            while (t < f.segEnd[k]) {
+                if (n == QA_PAULI_MAX_TERMS || a.nSeg == maxSegs) {
+                    launchPauliEvolve<R>(sv, a, stream);
+                    a = fresh(x);
+                    n = 0;
+                }
+                const int seg = a.nSeg++;
+                a.segIm[seg] = f.segIm[k] ? 1 : 0;
+                while (t < f.segEnd[k] && n < QA_PAULI_MAX_TERMS) {
+                    a.z[n] = f.z[t];
+                    a.w[n++] = f.w[t++];
+                }
+                a.segEnd[seg] = n;
+                // a one-term segment: the host's cos / sin of its constant |angle|
+                const int first = seg ? a.segEnd[seg - 1] : 0;
+                if (n - first == 1) {
+                    a.segCos[seg] = std::cos(a.w[first]);
+                    a.segSin[seg] = std::sin(a.w[first]);
+                }
+            }
+        }
+        launchPauliEvolve<R>(sv, a, stream);
+    }
+    if (phasePending) {
+        // nothing but identities: the diagonal kernel with an empty segment
+        PauliEvolveArgs a = fresh(0u);
+        a.nSeg = 1;
+        launchPauliEvolve<R>(sv, a, stream);
+    }
+}
+
+template <typename R>
+void QEngineHIP<R>::PauliRotation(
+    const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis, double theta)
+{
+    const PauliCanonSum c
+        = canonicalizePauliSum({ PauliTerm{ 1.0, bits, paulis } }, qubitCount, "PauliRotation");
+    pauliEvolveRun(c, pauliEvolvePlan(c, theta, 1, 1));
+}
+
+template <typename R>
+void QEngineHIP<R>::EvolvePauliSum(
+    const std::vector<PauliTerm>& terms, double time, int steps, int order)
+{
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "EvolvePauliSum");
+    pauliEvolveRun(c, pauliEvolvePlan(c, time, steps, order));
+}
+
 template <typename R> std::pair<double, bitCapInt> QEngineHIP<R>::argMax()
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));

@@ -205,6 +205,12 @@ public:
     double VariancePauliAll(
         const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
     double ExpectationPauliSum(const std::vector<PauliTerm>& terms) override;
+    // Pauli rotations and Pauli-sum evolution: one in-place read-and-write
+    // pass per planned pass (pauliEvolvePlan, qengine.hpp), no host sync
+    void PauliRotation(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
+        double theta) override;
+    void EvolvePauliSum(
+        const std::vector<PauliTerm>& terms, double time, int steps = 1, int order = 1) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;
@@ -266,6 +272,7 @@ protected:
     void resizeState(bitCapInt nAmps, cplx<R>* newBuf); // replace buffer
     double reduceSum(int op, const ReduceArgs& a);
     double pauliGroupsSum(const std::vector<PauliGroup>& groups);
+    void pauliEvolveRun(const PauliCanonSum& c, const PauliEvolvePlan& plan);
     // string with X/Y factors -> value; false when the generic lowering must answer
     bool pauliStringNative(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
         const char* what, double& value);

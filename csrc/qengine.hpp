@@ -77,15 +77,16 @@ inline PauliGroup pauliStringGroup(bitCapInt x, bitCapInt z, double coeff)
 }
 
 // Drop identities, merge equal (x, z), group by x. Terms are validated first.
-inline PauliCanonSum canonicalizePauliSum(const std::vector<PauliTerm>& terms, bitLenInt qubitCount)
+inline PauliCanonSum canonicalizePauliSum(const std::vector<PauliTerm>& terms, bitLenInt qubitCount,
+    const char* what = "ExpectationPauliSum")
 {
-    validatePauliTerms(terms, qubitCount);
+    validatePauliTerms(terms, qubitCount, what);
     std::map<std::pair<bitCapInt, bitCapInt>, double> merged;
     PauliCanonSum out;
     for (const PauliTerm& t : terms) {
         bitCapInt x, z;
         if (!pauliStringMasks(t.bits, t.paulis, qubitCount, x, z))
-            throw QrackError("ExpectationPauliSum: qubit out of range");
+            throw QrackError(std::string(what) + ": qubit out of range");
         if (!x && !z) {
             out.identity += t.coeff;
         } else {
@@ -101,6 +102,107 @@ inline PauliCanonSum canonicalizePauliSum(const std::vector<PauliTerm>& terms, b
         pauliGroupAdd(out.groups.back(), z, kv.second);
     }
     return out;
+}
+
+// ---- Pauli-sum evolution plan (shared by the dense engines) -----------------
+//
+// EvolvePauliSum is a product of per-term rotations (qinterface.hpp). All
+// terms of one group act inside the pairs {i, i^x}, and each parity set of a
+// group commutes, so one in-place pass over the state serves a run of
+// consecutive factors of one group. A pass is a short list of segments, each
+// one parity set rotated by its own tau:
+//   re set: (a, b) <- (c a - i s b, c b - i s a),  c + i s = e^{i tau wr(i)}
+//   im set: (a, b) <- (c a - s b,   c b + s a),    c + i s = e^{i tau wi(i)}
+// with a = psi[i], b = psi[i^x], i in the half-space with the top bit of x
+// clear, and wr / wi the signed weight sums of the set at i. The x = 0 group
+// is diagonal: psi[i] *= e^{-i tau wr(i)}.
+//
+// Adjacent passes on one group merge. Segments of the same set add their
+// angles; the two sets of a mixed group do not commute, so there the merged
+// pass keeps them as alternating segments (re im re at the turn-around of a
+// second-order step, im re im across a step boundary) — still one pass.
+struct PauliEvolveSeg {
+    bool im;    // which parity set of the group
+    double tau; // rotation angle per unit weight
+};
+
+struct PauliEvolvePass {
+    size_t group; // index into PauliCanonSum::groups
+    std::vector<PauliEvolveSeg> segs;
+};
+
+struct PauliEvolvePlan {
+    double phase = 0; // the state is also multiplied by e^{-i phase}
+    std::vector<PauliEvolvePass> passes;
+};
+
+// segments one pass may hold; a longer alternating run starts a new pass
+constexpr size_t PAULI_EVOLVE_MAX_SEGS = 4;
+
+inline PauliEvolvePlan pauliEvolvePlan(const PauliCanonSum& c, double time, int steps, int order)
+{
+    if (order != 1 && order != 2) throw QrackError("EvolvePauliSum: order must be 1 or 2");
+    if (steps < 1) throw QrackError("EvolvePauliSum: steps must be at least 1");
+    PauliEvolvePlan plan;
+    // the identity term commutes with everything: one scalar for the whole call
+    plan.phase = time * c.identity;
+    struct Factor {
+        size_t group;
+        bool im;
+    };
+    std::vector<Factor> forward;
+    for (size_t g = 0; g < c.groups.size(); ++g) {
+        if (!c.groups[g].re.empty()) forward.push_back({ g, false });
+        if (!c.groups[g].im.empty()) forward.push_back({ g, true });
+    }
+    const double tau = time / steps;
+    auto push = [&plan](const Factor& f, double t) {
+        if (!plan.passes.empty() && plan.passes.back().group == f.group) {
+            std::vector<PauliEvolveSeg>& segs = plan.passes.back().segs;
+            if (segs.back().im == f.im) {
+                segs.back().tau += t;
+                return;
+            }
+            if (segs.size() < PAULI_EVOLVE_MAX_SEGS) {
+                segs.push_back({ f.im, t });
+                return;
+            }
+        }
+        plan.passes.push_back({ f.group, { { f.im, t } } });
+    };
+    for (int s = 0; s < steps; ++s) {
+        if (order == 1) {
+            for (const Factor& f : forward) push(f, tau);
+        } else {
+            for (const Factor& f : forward) push(f, tau / 2);
+            for (size_t k = forward.size(); k-- > 0u;) push(forward[k], tau / 2);
+        }
+    }
+    return plan;
+}
+
+// Flatten one pass into (z, tau * w) entries, segment by segment, for the
+// engines' per-pair loops. segEnd[k] is the end of segment k in the list.
+struct PauliEvolveFlat {
+    std::vector<bitCapInt> z;
+    std::vector<double> w;
+    std::vector<size_t> segEnd;
+    std::vector<bool> segIm;
+};
+
+inline PauliEvolveFlat pauliEvolveFlatten(const PauliCanonSum& c, const PauliEvolvePass& p)
+{
+    PauliEvolveFlat f;
+    const PauliGroup& g = c.groups[p.group];
+    for (const PauliEvolveSeg& s : p.segs) {
+        for (const PauliCanonTerm& t : (s.im ? g.im : g.re)) {
+            f.z.push_back(t.z);
+            f.w.push_back(s.tau * t.w);
+        }
+        f.segEnd.push_back(f.z.size());
+        f.segIm.push_back(s.im);
+    }
+    return f;
 }
 
 template <typename R> class QEngine;

@@ -646,6 +646,91 @@ template <typename R> double QEngineCPU<R>::ExpectationPauliSum(const std::vecto
     return e;
 }
 
+// ---- Pauli rotations and Pauli-sum evolution (plan: qengine.hpp) -------------
+
+template <typename R>
+void QEngineCPU<R>::pauliEvolveRun(const PauliCanonSum& c, const PauliEvolvePlan& plan)
+{
+    cplx<R>* sv = stateVec.data();
+    // the identity phase rides on the first pass, or is one scalar multiply
+    bool phasePending = plan.phase != 0;
+    const cplx<R> ph((R)std::cos(plan.phase), (R)-std::sin(plan.phase));
+    for (const PauliEvolvePass& pass : plan.passes) {
+        const PauliEvolveFlat f = pauliEvolveFlatten(c, pass);
+        const bitCapInt* z = f.z.data();
+        const double* w = f.w.data();
+        const size_t nSeg = f.segEnd.size();
+        size_t segEnd[PAULI_EVOLVE_MAX_SEGS];
+        bool segIm[PAULI_EVOLVE_MAX_SEGS];
+        for (size_t k = 0; k < nSeg; ++k) {
+            segEnd[k] = f.segEnd[k];
+            segIm[k] = f.segIm[k];
+        }
+        const bool doPhase = phasePending;
+        phasePending = false;
+        const bitCapInt x = c.groups[pass.group].x;
+        if (!x) {
+            // diagonal group: its segments are all of the re set and were merged
+            const size_t n = f.z.size();
+            this->par_for(0, maxQPower, [=](const bitCapInt& i, unsigned) {
+                double ang = 0;
+                for (size_t t = 0; t < n; ++t) ang += __builtin_parityll(i & z[t]) ? -w[t] : w[t];
+                cplx<R> v = cplx<R>((R)std::cos(ang), (R)-std::sin(ang)) * sv[i];
+                if (doPhase) v = ph * v;
+                sv[i] = v;
+            });
+            continue;
+        }
+        const bitCapInt topPow = pow2(log2Ocl(x));
+        this->par_for(0, maxQPower >> 1u, [=](const bitCapInt& j, unsigned) {
+            const bitCapInt i = insertZeroBit(j, topPow);
+            cplx<R> a = sv[i];
+            cplx<R> b = sv[i ^ x];
+            size_t t = 0;
+            for (size_t k = 0; k < nSeg; ++k) {
+                double ang = 0;
+                for (; t < segEnd[k]; ++t) ang += __builtin_parityll(i & z[t]) ? -w[t] : w[t];
+                const R cs = (R)std::cos(ang), sn = (R)std::sin(ang);
+                if (segIm[k]) {
+                    const cplx<R> na(cs * a.re - sn * b.re, cs * a.im - sn * b.im);
+                    b = cplx<R>(cs * b.re + sn * a.re, cs * b.im + sn * a.im);
+                    a = na;
+                } else {
+                    const cplx<R> na(cs * a.re + sn * b.im, cs * a.im - sn * b.re);
+                    b = cplx<R>(cs * b.re + sn * a.im, cs * b.im - sn * a.re);
+                    a = na;
+                }
+            }
+            if (doPhase) {
+                a = ph * a;
+                b = ph * b;
+            }
+            sv[i] = a;
+            sv[i ^ x] = b;
+        });
+    }
+    if (phasePending) {
+        this->par_for(0, maxQPower, [=](const bitCapInt& i, unsigned) { sv[i] = ph * sv[i]; });
+    }
+}
+
+template <typename R>
+void QEngineCPU<R>::PauliRotation(
+    const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis, double theta)
+{
+    const PauliCanonSum c
+        = canonicalizePauliSum({ PauliTerm{ 1.0, bits, paulis } }, qubitCount, "PauliRotation");
+    pauliEvolveRun(c, pauliEvolvePlan(c, theta, 1, 1));
+}
+
+template <typename R>
+void QEngineCPU<R>::EvolvePauliSum(
+    const std::vector<PauliTerm>& terms, double time, int steps, int order)
+{
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "EvolvePauliSum");
+    pauliEvolveRun(c, pauliEvolvePlan(c, time, steps, order));
+}
+
 template <typename R> bool QEngineCPU<R>::ForceMParity(bitCapInt mask, bool result, bool doForce)
 {
     if (!mask) return false;

@@ -96,6 +96,12 @@ public:
     double VariancePauliAll(
         const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
     double ExpectationPauliSum(const std::vector<PauliTerm>& terms) override;
+    // Pauli rotations and Pauli-sum evolution: one in-place sweep per planned
+    // pass (pauliEvolvePlan, qengine.hpp), weights and angles in double
+    void PauliRotation(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
+        double theta) override;
+    void EvolvePauliSum(
+        const std::vector<PauliTerm>& terms, double time, int steps = 1, int order = 1) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;
@@ -161,6 +167,7 @@ protected:
     bitCapInt SampleOnce();
     void QftColumn(bitLenInt start, bitLenInt col, int sign, bool pre);
     double pauliGroupSum(const PauliGroup& g);
+    void pauliEvolveRun(const PauliCanonSum& c, const PauliEvolvePlan& plan);
     bool pauliStringNative(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
         const char* what, double& value);
 

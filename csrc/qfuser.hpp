@@ -190,6 +190,18 @@ public:
         FlushAll();
         return inner->ExpectationPauliSum(t);
     }
+    void PauliRotation(
+        const std::vector<bitLenInt>& b, const std::vector<Pauli>& p, double theta) override
+    {
+        FlushAll();
+        inner->PauliRotation(b, p, theta);
+    }
+    void EvolvePauliSum(
+        const std::vector<PauliTerm>& t, double time, int steps = 1, int order = 1) override
+    {
+        FlushAll();
+        inner->EvolvePauliSum(t, time, steps, order);
+    }
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override { FlushAll(); return inner->TrySeparate(q); }

@@ -4,6 +4,7 @@
 // shares. The lowerings here are textbook circuit identities written fresh
 // for this build; engines override the hot paths with direct kernels.
 #include "qinterface.hpp"
+#include "qengine.hpp" // Pauli-sum canonical form and evolution plan
 
 #include <algorithm>
 #include <cstring>
@@ -701,6 +702,66 @@ template <typename R> double QInterface<R>::ExpectationPauliSum(const std::vecto
     double e = 0;
     for (const PauliTerm& t : terms) e += t.coeff * PauliExpectation(t.bits, t.paulis);
     return e;
+}
+
+template <typename R>
+void QInterface<R>::PauliRotation(
+    const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis, double theta)
+{
+    validatePauliTerms({ PauliTerm{ 1.0, bits, paulis } }, qubitCount, "PauliRotation");
+    // X = H Z H and Y = S H Z H S^dagger, so rotate the X/Y qubits into the Z
+    // basis, turn the parity of the support by exp(-i theta Z..Z) and rotate back
+    bitCapInt mask = 0;
+    for (size_t i = 0; i < bits.size(); ++i) {
+        if (paulis[i] == PauliI) continue;
+        mask |= pow2(bits[i]);
+        if (paulis[i] == PauliY) IS(bits[i]);
+        if (paulis[i] != PauliZ) H(bits[i]);
+    }
+    if (mask) {
+        // PhaseParity(r) is exp(-i r/2 Z..Z), global phase included
+        PhaseParity((R)(2 * theta), mask);
+    } else {
+        // the identity string: PhaseParity has nothing to act on, so the
+        // global phase e^{-i theta} goes onto both levels of qubit 0
+        const cplx<R> f((R)std::cos(theta), (R)-std::sin(theta));
+        Phase(f, f, 0);
+    }
+    for (size_t i = 0; i < bits.size(); ++i) {
+        if (paulis[i] == PauliI || paulis[i] == PauliZ) continue;
+        H(bits[i]);
+        if (paulis[i] == PauliY) S(bits[i]);
+    }
+}
+
+template <typename R>
+void QInterface<R>::EvolvePauliSum(
+    const std::vector<PauliTerm>& terms, double time, int steps, int order)
+{
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "EvolvePauliSum");
+    const PauliEvolvePlan plan = pauliEvolvePlan(c, time, steps, order);
+    if (plan.phase != 0) PauliRotation({}, {}, plan.phase);
+    std::vector<bitLenInt> bits;
+    std::vector<Pauli> paulis;
+    for (const PauliEvolvePass& pass : plan.passes) {
+        const PauliGroup& g = c.groups[pass.group];
+        for (const PauliEvolveSeg& seg : pass.segs) {
+            for (const PauliCanonTerm& t : (seg.im ? g.im : g.re)) {
+                bits.clear();
+                paulis.clear();
+                // the canonical masks hold qubits below 64 only
+                for (bitLenInt q = 0; q < qubitCount && q < 64u; ++q) {
+                    const unsigned code = (unsigned)((g.x >> q) & 1u) | ((unsigned)((t.z >> q) & 1u) << 1u);
+                    if (!code) continue;
+                    bits.push_back(q);
+                    paulis.push_back((Pauli)code);
+                }
+                // t.w carries i^ny; the string's own coefficient is w / i^(ny & 2)
+                const int ny = __builtin_popcountll(g.x & t.z) & 3;
+                PauliRotation(bits, paulis, seg.tau * ((ny & 2) ? -t.w : t.w));
+            }
+        }
+    }
 }
 
 // ---- ALU defaults ----------------------------------------------------------

@@ -28,17 +28,19 @@ struct PauliTerm {
     std::vector<Pauli> paulis;
 };
 
-// ExpectationPauliSum argument check, shared by every implementation
-inline void validatePauliTerms(const std::vector<PauliTerm>& terms, bitLenInt qubitCount)
+// Pauli-term argument check, shared by every implementation; `what` names the
+// calling method in the error text
+inline void validatePauliTerms(const std::vector<PauliTerm>& terms, bitLenInt qubitCount,
+    const char* what = "ExpectationPauliSum")
 {
+    const std::string w(what);
     for (const PauliTerm& t : terms) {
-        if (t.bits.size() != t.paulis.size()) throw QrackError("ExpectationPauliSum: size mismatch");
+        if (t.bits.size() != t.paulis.size()) throw QrackError(w + ": size mismatch");
         for (size_t i = 0; i < t.bits.size(); ++i) {
-            if (t.bits[i] >= qubitCount) throw QrackError("ExpectationPauliSum: qubit out of range");
-            if ((unsigned)t.paulis[i] > 3u) throw QrackError("ExpectationPauliSum: bad Pauli code");
+            if (t.bits[i] >= qubitCount) throw QrackError(w + ": qubit out of range");
+            if ((unsigned)t.paulis[i] > 3u) throw QrackError(w + ": bad Pauli code");
             for (size_t j = 0; j < i; ++j) {
-                if (t.bits[j] == t.bits[i])
-                    throw QrackError("ExpectationPauliSum: qubit repeated in a term");
+                if (t.bits[j] == t.bits[i]) throw QrackError(w + ": qubit repeated in a term");
             }
         }
     }
@@ -737,6 +739,28 @@ public:
     // term. Default lowering: one PauliExpectation per term; the dense
     // engines answer the whole sum with one read-only pass per X/Y mask.
     virtual double ExpectationPauliSum(const std::vector<PauliTerm>& terms);
+    // exp(-i theta P), exactly and with its global phase, P the tensor product
+    // of the listed Paulis (codes as in PauliExpectation). Since
+    // RZ(a) = exp(-i a/2 Z), PauliRotation({q}, {PauliZ}, theta) is
+    // RZ(2 theta, q); the Exp* family is a different thing (a phase factor
+    // times the operator). An all-identity string is the global phase
+    // e^{-i theta}. Throws QrackError on a size mismatch, a bad code, or a
+    // qubit out of range or repeated. Default lowering: basis changes on the
+    // X/Y qubits around PhaseParity on the support.
+    virtual void PauliRotation(
+        const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis, double theta);
+    // Product-formula evolution under H = sum_t coeff_t P_t. With c the
+    // canonical sum (identities dropped into c.identity, equal strings merged,
+    // groups ascending in the X/Y mask, each group's real-weight terms before
+    // its imaginary-weight ones), S1(tau) applies exp(-i tau coeff_t P_t) term
+    // by term in that order and S2(tau) is S1(tau/2) followed by the same
+    // factors in reverse order. The call applies
+    //   e^{-i time c.identity} S_order(time/steps)^steps.
+    // Every layer applies exactly this product of per-term rotations: the
+    // default lowering loops PauliRotation, the dense engines do one in-place
+    // pass per X/Y mask. order must be 1 or 2 and steps >= 1.
+    virtual void EvolvePauliSum(
+        const std::vector<PauliTerm>& terms, double time, int steps = 1, int order = 1);
     // product observable squares to identity: Var = 1 - E^2
     double PauliProductVariance(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis)
     {

@@ -44,6 +44,18 @@ public:
         QInterface<R>::Mtrx1qBatch(targets, mtrxs);
     }
 
+    // likewise the Pauli rotations: the generic lowering, gate by gate
+    void PauliRotation(
+        const std::vector<bitLenInt>& b, const std::vector<Pauli>& p, double theta) override
+    {
+        QInterface<R>::PauliRotation(b, p, theta);
+    }
+    void EvolvePauliSum(
+        const std::vector<PauliTerm>& t, double time, int steps = 1, int order = 1) override
+    {
+        QInterface<R>::EvolvePauliSum(t, time, steps, order);
+    }
+
     void Mtrx(const cplx<R>* m, bitLenInt t) override
     {
         inner->Mtrx(m, t);

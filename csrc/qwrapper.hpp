@@ -153,6 +153,16 @@ public:
     {
         return inner->ExpectationPauliSum(t);
     }
+    void PauliRotation(
+        const std::vector<bitLenInt>& b, const std::vector<Pauli>& p, double theta) override
+    {
+        inner->PauliRotation(b, p, theta);
+    }
+    void EvolvePauliSum(
+        const std::vector<PauliTerm>& t, double time, int steps = 1, int order = 1) override
+    {
+        inner->EvolvePauliSum(t, time, steps, order);
+    }
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override { return inner->TrySeparate(q); }

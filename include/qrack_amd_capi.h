@@ -90,6 +90,14 @@ double qrack_joint_ensemble_probability(quid sid, const int* paulis, const uint6
  * (Pauli codes 0=I 1=X 2=Z 3=Y) */
 double qrack_expectation_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
     const uint64_t* termLens, const uint64_t* qs, const int* paulis);
+/* exp(-i theta P), global phase included, P the product of the listed Paulis
+ * (so a lone Z is RZ(2 theta)); an all-identity string is the phase e^{-i theta} */
+void qrack_pauli_rotation(quid sid, const int* paulis, const uint64_t* qs, uint64_t n, double theta);
+/* product-formula evolution exp(-i time H), H laid out as for
+ * qrack_expectation_pauli_sum: `steps` Trotter steps of order 1 or 2 */
+void qrack_evolve_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, double time, int steps,
+    int order);
 
 /* QFT */
 void qrack_qft(quid sid, uint64_t start, uint64_t length);

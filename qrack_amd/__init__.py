@@ -24,6 +24,7 @@ from qrack_amd._qrack import (  # noqa: F401
     profile_report,
     profile_reset,
     qft_pass_plan,
+    pauli_evolve_plan,
     save_stabilizer_F,
     save_stabilizer_D,
     load_stabilizer_F,

@@ -131,7 +131,31 @@ int main()
             return 1;
         } catch (const QrackError&) {
         }
+        // the one-pass evolution against the generic lowering of the same
+        // product (QUnit over the CPU engine), second order so that passes merge
+        auto g = CreateStack<float>(n, { "qunit", "cpu" }, 0, 4, -1, 1);
+        for (bitLenInt i = 0; i < n; ++i) g->RY(0.3f + 0.1f * (float)i, i);
+        for (bitLenInt i = 0; i + 1 < n; ++i) g->CNOT(i, i + 1);
+        p->EvolvePauliSum(terms, 0.1, 3, 2);
+        g->EvolvePauliSum(terms, 0.1, 3, 2);
+        p->PauliRotation(all, mixed, 0.2);
+        g->PauliRotation(all, mixed, 0.2);
+        std::vector<cplx<float>> sp(pow2(n)), sg(pow2(n));
+        p->GetQuantumState(sp.data());
+        g->GetQuantumState(sg.data());
+        for (size_t k = 0; k < sp.size(); ++k) {
+            if (std::abs(sp[k].re - sg[k].re) > 1e-4f || std::abs(sp[k].im - sg[k].im) > 1e-4f) {
+                std::printf("FAIL: pauli evolve %u at %zu\n", n, k);
+                return 1;
+            }
+        }
+        try {
+            p->EvolvePauliSum(terms, 0.1, 0, 1);
+            std::printf("FAIL: steps = 0 accepted\n");
+            return 1;
+        } catch (const QrackError&) {
+        }
     }
-    std::printf("ok: pauli sum\n");
+    std::printf("ok: pauli sum and evolution\n");
     return 0;
 }
