@@ -22,6 +22,7 @@
 #include "hip/qengine_hip.hpp"
 #endif
 #include "hip/qft_plan.hpp"
+#include "hip/rdm_plan.hpp"
 
 namespace py = pybind11;
 using namespace qrack_amd;
@@ -791,7 +792,26 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
             auto* p = reinterpret_cast<cplx<R>*>(out.mutable_data());
             for (int i = 0; i < 4; ++i) p[i] = rho[i];
             return out;
-        });
+        })
+        .def(
+            "reduced_density_matrix",
+            [](QI& q, std::vector<long> qubits) {
+                std::vector<bitLenInt> qs;
+                for (long b : qubits) {
+                    if (b < 0 || b >= (long)q.GetQubitCount()) {
+                        throw QrackError("GetReducedDensityMatrix: qubit out of range");
+                    }
+                    qs.push_back((bitLenInt)b);
+                }
+                validateRdmQubits(qs, q.GetQubitCount());
+                const py::ssize_t D = (py::ssize_t)1 << qs.size();
+                py::array_t<std::complex<double>> out({ D, D });
+                q.GetReducedDensityMatrix(qs, reinterpret_cast<cplx<double>*>(out.mutable_data()));
+                return out;
+            },
+            py::arg("qubits"),
+            "reduced density matrix of the listed qubits, complex128 (D, D) with D = 2^k; bit j of "
+            "a row or column index is the value of qubits[j]");
 }
 
 template <typename R> static void bindExtras(py::module_& m, const char* suffix)
@@ -931,6 +951,42 @@ PYBIND11_MODULE(_qrack, m)
             return out;
         },
         py::arg("length"), py::arg("width"), py::arg("precision"), py::arg("midmax") = 9);
+    // the HIP engine's reduced-density-matrix schedule; needs no GPU
+    m.def(
+        "rdm_pass_plan",
+        [](int width, std::vector<long> qubits, const std::string& precision) {
+            if (precision != "fp32" && precision != "fp64") {
+                throw std::invalid_argument("rdm_pass_plan: precision must be fp32 or fp64");
+            }
+            if (width < 1 || width > 64) throw std::invalid_argument("rdm_pass_plan: need 1 <= width <= 64");
+            std::vector<bitLenInt> qs;
+            for (long b : qubits) {
+                if (b < 0 || b >= width) throw QrackError("rdm_pass_plan: qubit out of range");
+                qs.push_back((bitLenInt)b);
+            }
+            validateRdmQubits(qs, (bitLenInt)width);
+            const RdmPlan p = rdmPassPlan(
+                width, std::vector<int>(qubits.begin(), qubits.end()), precision == "fp32" ? 4 : 8);
+            py::list launches;
+            for (const RdmLaunch& l : p.launches) launches.append(py::make_tuple(l.a, l.b));
+            py::dict d;
+            d["regime"] = rdmRegimeName(p.regime);
+            d["tile_bits"] = p.tileBits;
+            d["block_bits"] = p.blockBits;
+            d["tile_address_bits"] = p.tileAddrBits;
+            d["cross_address_bits"] = p.crossAddrBits;
+            d["launches"] = launches;
+            return d;
+        },
+        py::arg("width"), py::arg("qubits"), py::arg("precision"),
+        "launches the HIP engine walks for reduced_density_matrix(qubits): the regime "
+        "(\"register\" | \"tile\" | \"wide\"), the kept qubits a launch resolves itself, those the "
+        "launch list enumerates, and the (row, column) block values of every launch");
+    m.attr("RDM_MAX_QUBITS") = (int)QA_RDM_MAX_QUBITS;
+    m.attr("RDM_REG_MAX") = (int)QA_RDM_REG_MAX;
+    m.attr("RDM_TILE_MAX") = (int)QA_RDM_TILE_MAX;
+    // longest run the HIP tile kernel sums in the engine's real type
+    m.attr("RDM_RUN") = (int)QA_RDM_RUN;
 #ifdef QRACK_AMD_HIP_ENGINE
     m.def("profile_report", []() {
         py::dict d;

@@ -556,6 +556,20 @@ double qrack_expectation_pauli_sum(quid sid, uint64_t nTerms, const double* coef
     });
 }
 
+void qrack_reduced_density_matrix(quid sid, const uint64_t* qs, uint64_t n, double* rho)
+{
+    guarded(sid, [&](SimSlot& s) {
+        std::vector<bitLenInt> bits;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (qs[i] >= s.Qubits()) throw QrackError("qrack_reduced_density_matrix: qubit out of range");
+            bits.push_back((bitLenInt)qs[i]);
+        }
+        validateRdmQubits(bits, (bitLenInt)s.Qubits());
+        // cplx<double> is two doubles: the caller's buffer is the matrix
+        FOR_SIM(s, q.GetReducedDensityMatrix(bits, reinterpret_cast<cplx<double>*>(rho)));
+    });
+}
+
 void qrack_pauli_rotation(
     quid sid, const int* paulis, const uint64_t* qs, uint64_t n, double theta)
 {

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace qrack_amd {
@@ -3775,6 +3776,341 @@ void launchPauliEvolve(cplx<R>* sv, const PauliEvolveArgs& a, hipStream_t stream
     }
 }
 
+// ---- reduced density matrices -----------------------------------------------------
+//
+// rho[a,b] = sum_e psi[e,a] conj(psi[e,b]) over the kept qubits in ascending
+// physical order (the engine permutes into the caller's order). Read-only:
+// every launch leaves one set of double partials per block, and k_rdm_fold
+// adds the sets in a fixed order. Products are formed in R; sums are double,
+// but for runs of at most QA_RDM_RUN rows in the tile kernel.
+
+// deposit the low bits of x at the set bits of mask, lowest first
+__device__ __forceinline__ bitCapInt rdmDeposit(bitCapInt x, bitCapInt mask)
+{
+    bitCapInt r = 0;
+    while (mask) {
+        const bitCapInt low = mask & (~mask + 1u);
+        if (x & 1u) r |= low;
+        x >>= 1u;
+        mask ^= low;
+    }
+    return r;
+}
+
+// one environment row into the packed triangle: entry (a, b > a) keeps its
+// real part at [a*D+b] and its imaginary part at [b*D+a]
+template <typename R, int D>
+__device__ __forceinline__ void rdmRowAdd(const R (&re)[D], const R (&im)[D], double (&acc)[D * D])
+{
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        acc[a * D + a] += (double)(re[a] * re[a] + im[a] * im[a]);
+#pragma unroll
+        for (int b = a + 1; b < D; ++b) {
+            acc[a * D + b] += (double)(re[a] * re[b] + im[a] * im[b]);
+            acc[b * D + a] += (double)(im[a] * re[b] - re[a] * im[b]);
+        }
+    }
+}
+
+// Register regime. MODE 0: fp64, one row per item; 1: fp32, qubit 0 in the
+// environment, a 16-byte load holds the same entry of two rows; 2: fp32, qubit
+// 0 kept, a load holds entries a and a+1 of one row (as k_pauli_group MODE 2)
+template <typename R, int K, int MODE>
+__global__ __launch_bounds__(QA_BLOCK) void k_rdm_reg(const cplx<R>* sv, RdmRegArgs a, double* partials)
+{
+    constexpr int D = 1 << K;
+    double acc[D * D];
+#pragma unroll
+    for (int t = 0; t < D * D; ++t) acc[t] = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < a.nItems; v += stride) {
+        bitCapInt i = (MODE == 1) ? (v << 1u) : v;
+#pragma unroll
+        for (int j = 0; j < K; ++j) i = ((i & ~(a.pows[j] - 1u)) << 1u) | (i & (a.pows[j] - 1u));
+        if constexpr (MODE == 0) {
+            R re[D], im[D];
+#pragma unroll
+            for (int x = 0; x < D; ++x) {
+                const double2 A = reinterpret_cast<const double2*>(sv)[i | a.off[x]];
+                re[x] = A.x;
+                im[x] = A.y;
+            }
+            rdmRowAdd<R, D>(re, im, acc);
+        } else if constexpr (MODE == 1) {
+            R re0[D], im0[D], re1[D], im1[D];
+#pragma unroll
+            for (int x = 0; x < D; ++x) {
+                const float4 A = reinterpret_cast<const float4*>(sv)[(i | a.off[x]) >> 1u];
+                re0[x] = A.x;
+                im0[x] = A.y;
+                re1[x] = A.z;
+                im1[x] = A.w;
+            }
+            rdmRowAdd<R, D>(re0, im0, acc);
+            rdmRowAdd<R, D>(re1, im1, acc);
+        } else {
+            R re[D], im[D];
+#pragma unroll
+            for (int x = 0; x < D; x += 2) {
+                const float4 A = reinterpret_cast<const float4*>(sv)[(i | a.off[x]) >> 1u];
+                re[x] = A.x;
+                im[x] = A.y;
+                re[x + 1] = A.z;
+                im[x + 1] = A.w;
+            }
+            rdmRowAdd<R, D>(re, im, acc);
+        }
+    }
+    // block fold in a fixed order: wave shuffle -> LDS -> one set of D*D doubles
+    __shared__ double waveSums[QA_BLOCK / 64][D * D];
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int t = 0; t < D * D; ++t) {
+        const double s = waveReduceSum(acc[t]);
+        if (lane == 0) waveSums[wid][t] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < D * D) {
+        double s = 0;
+        for (int w = 0; w < QA_BLOCK / 64; ++w) s += waveSums[w][threadIdx.x];
+        partials[(size_t)blockIdx.x * (D * D) + threadIdx.x] = s;
+    }
+}
+
+// Tile regime. The tile lies in LDS in physical address order, so the load is
+// a plain copy in 16-byte vectors; the kept bits are picked out when the
+// patches read it. A thread owns the 4x4 patch (pa, pb) of the KT-bit block
+// and, where there are fewer patches than threads, one of G row groups.
+// DIAG (row and column side are the same slice): only the patches with
+// pa <= pb exist, numbered row by row; the host mirrors the rest.
+// Partials: entry f = r * P + p of a block's set, r = (i*4 + j)*2 + (0: re,
+// 1: im) inside patch p (pa * (DT/4) + pb when every patch exists).
+//
+// Kept bits high in the tile put the patches of a wave whole rows apart, all
+// on one bank, so the low index bits are XOR-ed with the next ones (the QFT
+// tiles' swizzle). The map is linear over XOR, and a row index and a kept
+// offset share no bit: swz(row | off) = swz(row) ^ swz(off). Bit 0 stays, so
+// an fp32 pair still moves as one 16-byte vector.
+template <typename R> __device__ __forceinline__ uint32_t rdmSwz(uint32_t x)
+{
+    return (sizeof(R) == 4) ? (x ^ ((x >> 6) & 62u)) : (x ^ ((x >> 5) & 31u));
+}
+
+template <typename R, int KT, bool DIAG>
+__global__ __launch_bounds__(QA_BLOCK) void k_rdm_tile(const cplx<R>* sv, RdmTileArgs a, double* partials)
+{
+    static_assert(QA_BLOCK == 256, "patch layout assumes 256 threads");
+    using V = typename std::conditional<sizeof(R) == 4, float4, double2>::type;
+    using C = typename std::conditional<sizeof(R) == 4, float2, double2>::type;
+    constexpr int APV = (sizeof(R) == 4) ? 2 : 1; // amplitudes per 16-byte vector
+    constexpr int LB = (sizeof(R) == 4) ? 9 : 8;  // tile-index bits a block covers per trip
+    constexpr int DT = 1 << KT;
+    constexpr int NP = DT / 4;
+    constexpr int P = rdmTilePatches(KT, DIAG);
+    constexpr int G = QA_BLOCK / P;
+    extern __shared__ __attribute__((aligned(16))) unsigned char rdmLds[];
+    const int T = a.tileAddrBits;
+    const uint32_t tileAmps = 1u << T;
+    const C* tileA = reinterpret_cast<const C*>(rdmLds);
+    const C* tileB = DIAG ? tileA : tileA + tileAmps;
+    V* ldsA = reinterpret_cast<V*>(rdmLds);
+    V* ldsB = ldsA + tileAmps / APV;
+
+    const int tid = threadIdx.x;
+    const int p = tid % P;
+    const int g = tid / P; // G, the spare threads of a block, has no rows
+    int pa = p / NP, pb = p % NP;
+    if constexpr (DIAG) {
+        pa = 0;
+        pb = p;
+        while (pb >= NP - pa) { // row pa of the triangle has NP - pa patches
+            pb -= NP - pa;
+            ++pa;
+        }
+        pb += pa;
+    }
+    const uint32_t M = a.keptInTile;
+    const uint32_t EM = (tileAmps - 1u) & ~M;
+    uint32_t aOff[4], bOff[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        aOff[i] = rdmSwz<R>((uint32_t)rdmDeposit((bitCapInt)(pa * 4 + i), M));
+        bOff[i] = rdmSwz<R>((uint32_t)rdmDeposit((bitCapInt)(pb * 4 + i), M));
+    }
+    // group g takes rows [E g / G, E (g + 1) / G)
+    const int E = 1 << (T - KT);
+    const int rowLo = (g < G) ? E * g / G : E;
+    const int rowsPer = (g < G) ? E * (g + 1) / G - rowLo : 0;
+    const uint32_t rowStart = (uint32_t)rdmDeposit((bitCapInt)rowLo, EM);
+    const bitCapInt physTid = rdmDeposit((bitCapInt)(tid * APV), a.tileMask);
+    const uint32_t nVec = tileAmps / APV;
+
+    double acc[32];
+#pragma unroll
+    for (int r = 0; r < 32; ++r) acc[r] = 0;
+
+    for (bitCapInt tile = blockIdx.x; tile < a.nTiles; tile += gridDim.x) {
+        const bitCapInt base = rdmDeposit(tile, a.enumMask);
+        __syncthreads(); // the last tile's readers are done
+        for (uint32_t v0 = 0; v0 < nVec; v0 += QA_BLOCK) {
+            const uint32_t v = v0 + tid;
+            if (v < nVec) {
+                // v0 * APV has no bit below LB, tid * APV none at or above it
+                const bitCapInt phys
+                    = base | physTid | rdmDeposit((bitCapInt)(v0 * APV) >> LB, a.tileMaskHigh);
+                const uint32_t sw = rdmSwz<R>(v * APV) / APV;
+                ldsA[sw] = reinterpret_cast<const V*>(sv)[(phys | a.rowOff) / APV];
+                if constexpr (!DIAG) ldsB[sw] = reinterpret_cast<const V*>(sv)[(phys | a.colOff) / APV];
+            }
+        }
+        __syncthreads();
+        if (rowsPer > 0) {
+            uint32_t idx = rowStart;
+            for (int r0 = 0; r0 < rowsPer; r0 += QA_RDM_RUN) {
+                R run[32];
+#pragma unroll
+                for (int r = 0; r < 32; ++r) run[r] = 0;
+                const int rn = min(QA_RDM_RUN, rowsPer - r0);
+                for (int row = 0; row < rn; ++row) {
+                    C av[4], bv[4];
+                    const uint32_t si = rdmSwz<R>(idx);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        av[i] = tileA[si ^ aOff[i]];
+                        bv[i] = tileB[si ^ bOff[i]];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            run[(i * 4 + j) * 2] += av[i].x * bv[j].x + av[i].y * bv[j].y;
+                            run[(i * 4 + j) * 2 + 1] += av[i].y * bv[j].x - av[i].x * bv[j].y;
+                        }
+                    }
+                    idx = ((idx | ~EM) + 1u) & EM; // next row: carry across the kept bits
+                }
+#pragma unroll
+                for (int r = 0; r < 32; ++r) acc[r] += (double)run[r];
+            }
+        }
+    }
+
+    double* dst = partials + (size_t)blockIdx.x * (32 * P);
+    if constexpr (G == 1) {
+        if (tid < P) {
+#pragma unroll
+            for (int r = 0; r < 32; ++r) dst[r * P + p] = acc[r];
+        }
+    } else {
+        // the row groups add up in group order, in LDS
+        double* sh = reinterpret_cast<double*>(rdmLds);
+        for (int gg = 0; gg < G; ++gg) {
+            __syncthreads();
+            if (g == gg) {
+#pragma unroll
+                for (int r = 0; r < 32; ++r) sh[r * P + p] = (gg ? sh[r * P + p] : 0.0) + acc[r];
+            }
+        }
+        __syncthreads();
+        for (int f = tid; f < 32 * P; f += QA_BLOCK) dst[f] = sh[f];
+    }
+}
+
+// fold nSets sets of nEntries doubles in a fixed order: a wave takes 64
+// entries and a quarter of the sets, the four quarters add up in LDS
+__global__ __launch_bounds__(QA_BLOCK) void k_rdm_fold(const double* partials, int nSets, int nEntries, double* result)
+{
+    __shared__ double quarter[QA_BLOCK / 64][64];
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + lane;
+    const int lo = (int)((long)nSets * wid / (QA_BLOCK / 64));
+    const int hi = (int)((long)nSets * (wid + 1) / (QA_BLOCK / 64));
+    double s = 0;
+    if (e < nEntries) {
+        for (int k = lo; k < hi; ++k) s += partials[(size_t)k * nEntries + e];
+    }
+    quarter[wid][lane] = s;
+    __syncthreads();
+    if (wid == 0 && e < nEntries) {
+        double t = 0;
+        for (int w = 0; w < QA_BLOCK / 64; ++w) t += quarter[w][lane];
+        result[e] = t;
+    }
+}
+
+static inline int rdmGrid(bitCapInt blocks, int hardCap)
+{
+    bitCapInt b = std::min<bitCapInt>(blocks, (bitCapInt)hardCap);
+    const int cap = maxBlocks();
+    if (cap > 0 && b > (bitCapInt)cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+int rdmRegGrid(bitCapInt nItems) { return rdmGrid((nItems + QA_BLOCK - 1) / QA_BLOCK, QA_RDM_REG_GRID); }
+int rdmTileGrid(bitCapInt nTiles) { return rdmGrid(nTiles, QA_RDM_TILE_GRID); }
+
+static void launchRdmFold(const double* partialsDev, int nSets, int nEntries, double* resultDev,
+    hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_rdm_fold, dim3((nEntries + 63) / 64), dim3(QA_BLOCK), 0, stream,
+        partialsDev, nSets, nEntries, resultDev);
+}
+
+template <typename R>
+void launchRdmReg(const cplx<R>* sv, int k, bool keepsBit0, const RdmRegArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream)
+{
+    const int grid = rdmRegGrid(a.nItems);
+    const dim3 g(grid), b(QA_BLOCK);
+#define QA_RDM_REG(K)                                                                               \
+    do {                                                                                            \
+        if constexpr (sizeof(R) == 8) {                                                             \
+            hipLaunchKernelGGL((k_rdm_reg<R, K, 0>), g, b, 0, stream, sv, a, partialsDev);          \
+        } else if (keepsBit0) {                                                                     \
+            hipLaunchKernelGGL((k_rdm_reg<R, K, 2>), g, b, 0, stream, sv, a, partialsDev);          \
+        } else {                                                                                    \
+            hipLaunchKernelGGL((k_rdm_reg<R, K, 1>), g, b, 0, stream, sv, a, partialsDev);          \
+        }                                                                                           \
+    } while (0)
+    switch (k) {
+    case 1: QA_RDM_REG(1); break;
+    case 2: QA_RDM_REG(2); break;
+    case 3: QA_RDM_REG(3); break;
+    default: throw QrackError("launchRdmReg: no kernel for this many kept qubits");
+    }
+#undef QA_RDM_REG
+    launchRdmFold(partialsDev, grid, 1 << (2 * k), resultDev, stream);
+}
+
+template <typename R>
+void launchRdmTile(const cplx<R>* sv, int kt, const RdmTileArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream)
+{
+    const int grid = rdmTileGrid(a.nTiles);
+    const dim3 g(grid), b(QA_BLOCK);
+    const uint32_t lds = 32768u; // the tile, or two half tiles; the group fold fits inside
+#define QA_RDM_TILE(KT)                                                                             \
+    do {                                                                                            \
+        if (a.cross) {                                                                              \
+            hipLaunchKernelGGL((k_rdm_tile<R, KT, false>), g, b, lds, stream, sv, a, partialsDev);  \
+        } else {                                                                                    \
+            hipLaunchKernelGGL((k_rdm_tile<R, KT, true>), g, b, lds, stream, sv, a, partialsDev);   \
+        }                                                                                           \
+    } while (0)
+    switch (kt) {
+    case 4: QA_RDM_TILE(4); break;
+    case 5: QA_RDM_TILE(5); break;
+    case 6: QA_RDM_TILE(6); break;
+    default: throw QrackError("launchRdmTile: no kernel for this many kept qubits");
+    }
+#undef QA_RDM_TILE
+    launchRdmFold(partialsDev, grid, 32 * rdmTilePatches(kt, !a.cross), resultDev, stream);
+}
+
 // ---- explicit instantiations ---------------------------------------------------
 
 #define QA_INSTANTIATE(R)                                                                           \
@@ -3787,6 +4123,10 @@ void launchPauliEvolve(cplx<R>* sv, const PauliEvolveArgs& a, hipStream_t stream
     template int launchArgMax<R>(const cplx<R>*, bitCapInt, double*, bitCapInt*, hipStream_t);      \
     template void launchPauliGroup<R>(const cplx<R>*, const PauliArgs&, double*, double*, hipStream_t); \
     template void launchPauliEvolve<R>(cplx<R>*, const PauliEvolveArgs&, hipStream_t);              \
+    template void launchRdmReg<R>(                                                                  \
+        const cplx<R>*, int, bool, const RdmRegArgs&, double*, double*, hipStream_t);               \
+    template void launchRdmTile<R>(                                                                 \
+        const cplx<R>*, int, const RdmTileArgs&, double*, double*, hipStream_t);                    \
     template void launchNormalize<R>(cplx<R>*, bitCapInt, cplx<R>, R, hipStream_t);                 \
     template void launchApplyM<R>(cplx<R>*, bitCapInt, bitCapInt, bitCapInt, cplx<R>, hipStream_t); \
     template void launchApplyParity<R>(cplx<R>*, bitCapInt, bitCapInt, bool, cplx<R>, hipStream_t); \

@@ -10,6 +10,7 @@
 #pragma once
 
 #include "../common/types.hpp"
+#include "rdm_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -135,7 +136,42 @@ struct PauliEvolveArgs {
     double w[QA_PAULI_MAX_TERMS];
 };
 
+// reduced density matrix, register regime (rdm_plan.hpp): kept powers
+// ascending, and the state offset of every kept index in that order
+struct RdmRegArgs {
+    bitCapInt pows[QA_RDM_REG_MAX];
+    bitCapInt off[1 << QA_RDM_REG_MAX];
+    bitCapInt nItems; // environment rows; row pairs in fp32 with qubit 0 not kept
+};
+
+// ... tile regime: one launch of the plan
+struct RdmTileArgs {
+    bitCapInt tileMask;     // state bits that address the tile: kept-in-tile + low environment
+    bitCapInt tileMaskHigh; // tileMask without the bits a block covers in one trip
+    bitCapInt enumMask;     // environment bits that number the tiles
+    bitCapInt rowOff;       // block bits at the row-side value
+    bitCapInt colOff;       // ... at the column-side value
+    bitCapInt nTiles;
+    uint32_t keptInTile;    // the kept bits, as a mask over the tile's own index
+    int tileAddrBits;       // T: a tile holds 2^T amplitudes
+    int cross;              // rowOff != colOff: two tiles
+};
+
 // ---- launches (all asynchronous on `stream`) -------------------------------
+
+// Reduced density matrix passes. Stage 1 leaves one set of double partials
+// per block in partialsDev (rdmRegGrid / rdmTileGrid sets of 4^k or
+// 32 * rdmTilePatches doubles), stage 2 folds them in a fixed order into
+// resultDev. Read sv only.
+int rdmRegGrid(bitCapInt nItems);
+int rdmTileGrid(bitCapInt nTiles);
+template <typename R>
+void launchRdmReg(const cplx<R>* sv, int k, bool keepsBit0, const RdmRegArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream);
+template <typename R>
+void launchRdmTile(const cplx<R>* sv, int kt, const RdmTileArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream);
+
 
 // One read-and-write pass: every amplitude is loaded once and stored once, by
 // exactly one thread.

@@ -156,6 +156,7 @@ template <typename R> QEngineHIP<R>::~QEngineHIP()
     releaseScratch();
     releaseTileSums();
     releaseAux();
+    releaseRdm();
     if (dPartials) hipFree(dPartials);
     if (dIdx) hipFree(dIdx);
     hipStreamDestroy(stream);
@@ -249,6 +250,33 @@ template <typename R> unsigned char* QEngineHIP<R>::uploadAux(size_t bytes)
     return dAux_;
 }
 
+template <typename R> void QEngineHIP<R>::releaseRdm()
+{
+    if (!dRdm_) return;
+    hipFree(dRdm_);
+    HipDeviceTracker::instance().sub(deviceId, rdmBytes_);
+    dRdm_ = nullptr;
+    rdmBytes_ = 0;
+}
+
+template <typename R> double* QEngineHIP<R>::rdmBuffer(size_t doubles)
+{
+    const size_t bytes = doubles * sizeof(double);
+    if (bytes <= rdmBytes_) return dRdm_;
+    QA_HIP_CHECK(hipStreamSynchronize(stream));
+    releaseRdm();
+    auto& tracker = HipDeviceTracker::instance();
+    tracker.add(deviceId, bytes);
+    const hipError_t err = hipMalloc(&dRdm_, bytes);
+    if (err != hipSuccess) {
+        dRdm_ = nullptr;
+        tracker.sub(deviceId, bytes);
+        QA_HIP_CHECK(err);
+    }
+    rdmBytes_ = bytes;
+    return dRdm_;
+}
+
 template <typename R> void QEngineHIP<R>::releaseTileSums()
 {
     if (dTileSums_) hipFree(dTileSums_);
@@ -312,6 +340,7 @@ template <typename R> void QEngineHIP<R>::SetDevice(int64_t devId)
     releaseScratch();
     releaseTileSums();
     releaseAux();
+    releaseRdm();
     freeDev(dState_, maxQPower);
     hipStreamDestroy(stream);
     hipFree(dPartials);
@@ -1295,6 +1324,160 @@ template <typename R> double QEngineHIP<R>::ExpectationPauliSum(const std::vecto
 {
     const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount);
     return c.identity + pauliGroupsSum(c.groups);
+}
+
+// ---- reduced density matrices --------------------------------------------------
+
+template <typename R>
+void QEngineHIP<R>::GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out)
+{
+    validateRdmQubits(qubits, qubitCount);
+    const int k = (int)qubits.size();
+    const size_t D = (size_t)1 << k;
+    if (basisPending_) {
+        // |perm><perm|: one diagonal entry, nothing to launch
+        std::fill(out, out + D * D, cplx<double>(0.0, 0.0));
+        size_t a = 0;
+        for (int j = 0; j < k; ++j) a |= (size_t)((basisPerm_ >> qubits[j]) & 1u) << j;
+        out[a * D + a] = cplx<double>(1.0, 0.0);
+        return;
+    }
+    const RdmPlan plan
+        = rdmPassPlan(qubitCount, std::vector<int>(qubits.begin(), qubits.end()), (int)sizeof(R));
+    // the kernels index the kept qubits in ascending order: caller index of
+    // every such index
+    std::vector<int> sorted(plan.tileBits);
+    sorted.insert(sorted.end(), plan.blockBits.begin(), plan.blockBits.end());
+    std::vector<uint32_t> cidx(D, 0);
+    for (int r = 0; r < k; ++r) {
+        const int j = (int)(std::find(qubits.begin(), qubits.end(), (bitLenInt)sorted[r]) - qubits.begin());
+        for (size_t s = 0; s < D; ++s) {
+            if ((s >> r) & 1u) cidx[s] |= 1u << j;
+        }
+    }
+    auto put = [&](size_t sa, size_t sb, double re, double im) {
+        const size_t ca = cidx[sa], cb = cidx[sb];
+        out[ca * D + cb] = cplx<double>(re, im);
+        out[cb * D + ca] = cplx<double>(re, -im);
+    };
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    HipProfScope prof("rdm", stream);
+    const cplx<R>* sv = rState();
+
+    if (plan.regime == RdmRegime::Register) {
+        RdmRegArgs a{};
+        for (int r = 0; r < k; ++r) a.pows[r] = pow2((bitLenInt)sorted[r]);
+        for (size_t s = 0; s < D; ++s) {
+            for (int r = 0; r < k; ++r) {
+                if ((s >> r) & 1u) a.off[s] |= a.pows[r];
+            }
+        }
+        const bool keepsBit0 = sorted[0] == 0;
+        a.nItems = maxQPower >> k;
+        // fp32 with qubit 0 in the environment: an item is a pair of rows
+        if (sizeof(R) == 4 && !keepsBit0) a.nItems >>= 1u;
+        const size_t nE = D * D;
+        const size_t grid = (size_t)rdmRegGrid(a.nItems);
+        double* buf = rdmBuffer((grid + 1u) * nE);
+        launchRdmReg<R>(sv, k, keepsBit0, a, buf, buf + grid * nE, stream);
+        std::vector<double> h(nE);
+        QA_HIP_CHECK(hipMemcpyAsync(
+            h.data(), buf + grid * nE, nE * sizeof(double), hipMemcpyDeviceToHost, stream));
+        Finish();
+        for (size_t sa = 0; sa < D; ++sa) {
+            put(sa, sa, h[sa * D + sa], 0.0);
+            for (size_t sb = sa + 1; sb < D; ++sb) put(sa, sb, h[sa * D + sb], h[sb * D + sa]);
+        }
+        return;
+    }
+
+    const int kt = (int)plan.tileBits.size();
+    bitCapInt tileKept = 0, keptAll = 0;
+    for (int q : plan.tileBits) tileKept |= pow2((bitLenInt)q);
+    for (int q : sorted) keptAll |= pow2((bitLenInt)q);
+    std::vector<bitLenInt> env;
+    for (bitLenInt q = 0; q < qubitCount; ++q) {
+        if (!(keptAll & pow2(q))) env.push_back(q);
+    }
+    auto makeArgs = [&](int T, bool cross) {
+        RdmTileArgs a{};
+        const size_t nLow = (size_t)(T - kt); // environment bits inside the tile
+        a.tileMask = tileKept;
+        for (size_t i = 0; i < env.size(); ++i) (i < nLow ? a.tileMask : a.enumMask) |= pow2(env[i]);
+        a.nTiles = ONE_BCI << (env.size() - nLow);
+        a.tileAddrBits = T;
+        a.cross = cross ? 1 : 0;
+        // a block of 256 threads covers 2^LB tile indices per trip
+        const int LB = sizeof(R) == 4 ? 9 : 8;
+        int pos = 0;
+        for (bitLenInt q = 0; q < qubitCount; ++q) {
+            if (!(a.tileMask & pow2(q))) continue;
+            if (tileKept & pow2(q)) a.keptInTile |= 1u << pos;
+            if (pos >= LB) a.tileMaskHigh |= pow2(q);
+            ++pos;
+        }
+        return a;
+    };
+    const RdmTileArgs diagArgs = makeArgs(plan.tileAddrBits, false);
+    const RdmTileArgs crossArgs = makeArgs(plan.crossAddrBits, true);
+    auto blockOff = [&](uint32_t v) {
+        bitCapInt o = 0;
+        for (size_t r = 0; r < plan.blockBits.size(); ++r) {
+            if ((v >> r) & 1u) o |= pow2((bitLenInt)plan.blockBits[r]);
+        }
+        return o;
+    };
+    const size_t DT = (size_t)1 << kt;
+    const size_t NP = DT / 4u;
+    const size_t nE = 2u * DT * DT; // stride of a result set; a diagonal launch fills less
+    const size_t grid = (size_t)std::max(rdmTileGrid(diagArgs.nTiles), rdmTileGrid(crossArgs.nTiles));
+    // results come back in batches: one copy and one sync up to 256 launches
+    const size_t batch = std::min<size_t>(plan.launches.size(), 256u);
+    double* buf = rdmBuffer((grid + batch) * nE);
+    double* results = buf + grid * nE;
+    std::vector<double> h(batch * nE);
+    for (size_t base = 0; base < plan.launches.size(); base += batch) {
+        const size_t n = std::min(batch, plan.launches.size() - base);
+        for (size_t l = 0; l < n; ++l) {
+            const RdmLaunch& L = plan.launches[base + l];
+            RdmTileArgs a = (L.a == L.b) ? diagArgs : crossArgs;
+            a.rowOff = blockOff(L.a);
+            a.colOff = blockOff(L.b);
+            launchRdmTile<R>(sv, kt, a, buf, results + l * nE, stream);
+        }
+        QA_HIP_CHECK(hipMemcpyAsync(
+            h.data(), results, n * nE * sizeof(double), hipMemcpyDeviceToHost, stream));
+        Finish();
+        for (size_t l = 0; l < n; ++l) {
+            const RdmLaunch& L = plan.launches[base + l];
+            const double* hl = h.data() + l * nE;
+            const bool diag = L.a == L.b;
+            const size_t P = (size_t)rdmTilePatches(kt, diag);
+            // a diagonal launch numbers the patches pa <= pb row by row, and
+            // the block is mirrored from its upper triangle
+            size_t pa = 0, pb = 0;
+            for (size_t p = 0; p < P; ++p) {
+                for (size_t ij = 0; ij < 16u; ++ij) {
+                    const size_t ta = pa * 4u + ij / 4u, tb = pb * 4u + ij % 4u;
+                    if (diag && ta > tb) continue;
+                    const double re = hl[(ij * 2u) * P + p];
+                    const double im = (diag && ta == tb) ? 0.0 : hl[(ij * 2u + 1u) * P + p];
+                    put(((size_t)L.a << kt) | ta, ((size_t)L.b << kt) | tb, re, im);
+                }
+                if (++pb == NP) {
+                    ++pa;
+                    pb = diag ? pa : 0;
+                }
+            }
+        }
+    }
+}
+
+template <typename R> void QEngineHIP<R>::GetReducedDensityMatrix(bitLenInt q, cplx<R>* out)
+{
+    cplx<double> rho[4];
+    GetReducedDensityMatrix(std::vector<bitLenInt>{ q }, rho);
+    for (int t = 0; t < 4; ++t) out[t] = cplx<R>((R)rho[t].re, (R)rho[t].im);
 }
 
 // ---- Pauli rotations and Pauli-sum evolution ---------------------------------

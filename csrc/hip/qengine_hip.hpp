@@ -205,6 +205,11 @@ public:
     double VariancePauliAll(
         const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
     double ExpectationPauliSum(const std::vector<PauliTerm>& terms) override;
+    // reduced density matrices: the launches of rdmPassPlan (rdm_plan.hpp),
+    // read-only, no clone, no scratch; a pending basis state is answered on
+    // the host. The single-qubit form is the k = 1 case.
+    void GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out) override;
+    void GetReducedDensityMatrix(bitLenInt q, cplx<R>* out) override;
     // Pauli rotations and Pauli-sum evolution: one in-place read-and-write
     // pass per planned pass (pauliEvolvePlan, qengine.hpp), no host sync
     void PauliRotation(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
@@ -276,6 +281,10 @@ protected:
     // string with X/Y factors -> value; false when the generic lowering must answer
     bool pauliStringNative(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
         const char* what, double& value);
+    // block partials and per-launch results of the reduced-density-matrix
+    // passes: accounted like the state, allocated on first use, grown on demand
+    double* rdmBuffer(size_t doubles);
+    void releaseRdm();
     std::pair<double, bitCapInt> argMax();
     std::vector<double> partProbs(bitLenInt start, bitLenInt length);
     bitCapInt sampleOnce(const std::vector<double>& chunkSums, bitCapInt chunkLen, double r,
@@ -340,6 +349,8 @@ private:
     bitCapInt tileSumsLen_ = 0;
     bool tileSumsValid_ = false;
     bool externView_ = false; // sticky: a raw pointer escaped this engine
+    double* dRdm_ = nullptr;
+    size_t rdmBytes_ = 0;
 };
 
 } // namespace qrack_amd

@@ -1087,65 +1087,28 @@ void OutProbs(uintq sid, real1_s* p)
     });
 }
 
-} // extern "C" (template helper needs C++ linkage)
-
-template <typename Rt>
-static void pcRdm(QInterface<Rt>& q, const std::vector<bitLenInt>& qv, real1_s* rdm)
-{
-    const bitLenInt nq = q.GetQubitCount();
-    const size_t n = qv.size();
-    const size_t dim = ((size_t)1) << n;
-    const bitCapInt np = pow2(nq);
-    std::vector<cplx<Rt>> sv((size_t)np);
-    q.GetQuantumState(sv.data());
-    std::vector<cplx<double>> m(dim * dim, cplx<double>(0, 0));
-    for (bitCapInt i = 0; i < np; ++i) {
-        // split index into (listed-bit pattern a, environment e)
-        size_t a = 0;
-        for (size_t b = 0; b < n; ++b) {
-            if ((i >> qv[b]) & 1u) a |= ((size_t)1 << b);
-        }
-        for (size_t b2 = 0; b2 < dim; ++b2) {
-            // partner index with listed bits set to pattern b2
-            bitCapInt j = i;
-            for (size_t b = 0; b < n; ++b) {
-                const bitCapInt p = pow2(qv[b]);
-                if ((b2 >> b) & 1u) {
-                    j |= p;
-                } else {
-                    j &= ~p;
-                }
-            }
-            const cplx<Rt>& x = sv[(size_t)i];
-            const cplx<Rt>& y = sv[(size_t)j];
-            // rho[a][b2] += <a,e| psi><psi |b2,e>
-            m[a * dim + b2] = m[a * dim + b2] +
-                cplx<double>((double)x.re, (double)x.im) *
-                    cplx<double>((double)y.re, (double)-y.im);
-        }
-    }
-    // each (i, b2) pair was accumulated once per environment via the i loop,
-    // but i runs over ALL states: entries got counted 2^n times (once per
-    // listed-bit pattern of i with same environment) — divide back
-    for (size_t k = 0; k < dim * dim; ++k) m[k] = m[k] * (1.0 / (double)dim);
-    for (size_t k = 0; k < dim * dim; ++k) {
-        rdm[2 * k] = (real1_s)m[k].re;
-        rdm[2 * k + 1] = (real1_s)m[k].im;
-    }
-}
-
-extern "C" {
-
 void OutReducedDensityMatrix(uintq sid, uintq n, uintq* qs, real1_s* rdm)
 {
     guarded((quid)sid, [&](SimSlot& s) {
         const std::vector<bitLenInt> qv = mapv(s, n, qs);
-        if (n > 12u || s.Qubits() > 26u) {
+        if (n > 12u) {
             s.error = 2;
             return;
         }
-        if (s.f) pcRdm<float>(*s.f, qv, rdm);
-        if (s.d) pcRdm<double>(*s.d, qv, rdm);
+        std::vector<cplx<double>> m(((size_t)1 << n) << n);
+        try {
+            if (s.f) s.f->GetReducedDensityMatrix(qv, m.data());
+            if (s.d) s.d->GetReducedDensityMatrix(qv, m.data());
+        } catch (const QrackError&) {
+            // the width cap of the generic lowering keeps its error code
+            if (s.Qubits() <= 26u) throw;
+            s.error = 2;
+            return;
+        }
+        for (size_t k = 0; k < m.size(); ++k) {
+            rdm[2 * k] = (real1_s)m[k].re;
+            rdm[2 * k + 1] = (real1_s)m[k].im;
+        }
     });
 }
 

@@ -646,6 +646,70 @@ template <typename R> double QEngineCPU<R>::ExpectationPauliSum(const std::vecto
     return e;
 }
 
+// ---- reduced density matrices --------------------------------------------------
+
+template <typename R>
+void QEngineCPU<R>::GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out)
+{
+    validateRdmQubits(qubits, qubitCount);
+    const cplx<R>* sv = stateVec.data();
+    const size_t k = qubits.size();
+    const size_t D = (size_t)1 << k;
+    const std::vector<bitCapInt> offV = rdmKeptOffsets(qubits);
+    const std::vector<bitCapInt> powV = rdmKeptPowers(qubits);
+    const bitCapInt* off = offV.data();
+    const bitCapInt* pows = powV.data();
+    const bitCapInt nEnv = maxQPower >> k;
+    // entry (a, b >= a) of the upper triangle: real part at [a*D+b], imaginary
+    // part at [b*D+a]; the diagonal holds its (real) value
+    auto addRow = [=](double* m, bitCapInt e) {
+        bitCapInt i = e;
+        for (size_t j = 0; j < k; ++j) i = insertZeroBit(i, pows[j]);
+        for (size_t a = 0; a < D; ++a) {
+            const cplx<R> x = sv[i | off[a]];
+            m[a * D + a] += (double)(x.re * x.re + x.im * x.im);
+            for (size_t b = a + 1; b < D; ++b) {
+                const cplx<R> y = sv[i | off[b]];
+                m[a * D + b] += (double)(x.re * y.re + x.im * y.im);
+                m[b * D + a] += (double)(x.im * y.re - x.re * y.im);
+            }
+        }
+    };
+    std::vector<double> total(D * D, 0.0);
+    // workers take fixed environment slices, so the result does not depend on
+    // scheduling; the private matrices are bounded to 64 MB in all
+    const bitCapInt bySize = std::max<bitCapInt>(1u, ((bitCapInt)1 << 23) / (D * D));
+    const bitCapInt byWork = std::max<bitCapInt>(1u, (nEnv * D * D) >> 16u);
+    const unsigned nw = (unsigned)std::min<bitCapInt>({ (bitCapInt)this->numCores(), bySize, byWork, nEnv });
+    if (nw <= 1) {
+        for (bitCapInt e = 0; e < nEnv; ++e) addRow(total.data(), e);
+    } else {
+        std::vector<double> priv((size_t)nw * D * D, 0.0);
+        double* pp = priv.data();
+        ThreadPool::instance().run(nw, [=](unsigned w) {
+            const bitCapInt lo = nEnv * w / nw, hi = nEnv * (w + 1u) / nw;
+            for (bitCapInt e = lo; e < hi; ++e) addRow(pp + (size_t)w * D * D, e);
+        });
+        for (unsigned w = 0; w < nw; ++w) {
+            for (size_t t = 0; t < D * D; ++t) total[t] += priv[(size_t)w * D * D + t];
+        }
+    }
+    for (size_t a = 0; a < D; ++a) {
+        out[a * D + a] = cplx<double>(total[a * D + a], 0.0);
+        for (size_t b = a + 1; b < D; ++b) {
+            out[a * D + b] = cplx<double>(total[a * D + b], total[b * D + a]);
+            out[b * D + a] = cplx<double>(total[a * D + b], -total[b * D + a]);
+        }
+    }
+}
+
+template <typename R> void QEngineCPU<R>::GetReducedDensityMatrix(bitLenInt q, cplx<R>* out)
+{
+    cplx<double> rho[4];
+    GetReducedDensityMatrix(std::vector<bitLenInt>{ q }, rho);
+    for (int t = 0; t < 4; ++t) out[t] = cplx<R>((R)rho[t].re, (R)rho[t].im);
+}
+
 // ---- Pauli rotations and Pauli-sum evolution (plan: qengine.hpp) -------------
 
 template <typename R>

@@ -96,6 +96,10 @@ public:
     double VariancePauliAll(
         const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis) override;
     double ExpectationPauliSum(const std::vector<PauliTerm>& terms) override;
+    // reduced density matrices: one read-only pass, no state copy; private
+    // per-worker matrices folded in worker order, so a repeat is bit-identical
+    void GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out) override;
+    void GetReducedDensityMatrix(bitLenInt q, cplx<R>* out) override;
     // Pauli rotations and Pauli-sum evolution: one in-place sweep per planned
     // pass (pauliEvolvePlan, qengine.hpp), weights and angles in double
     void PauliRotation(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,

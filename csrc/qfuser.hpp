@@ -190,6 +190,16 @@ public:
         FlushAll();
         return inner->ExpectationPauliSum(t);
     }
+    void GetReducedDensityMatrix(bitLenInt q, cplx<R>* out) override
+    {
+        FlushAll();
+        inner->GetReducedDensityMatrix(q, out);
+    }
+    void GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out) override
+    {
+        FlushAll();
+        inner->GetReducedDensityMatrix(qubits, out);
+    }
     void PauliRotation(
         const std::vector<bitLenInt>& b, const std::vector<Pauli>& p, double theta) override
     {

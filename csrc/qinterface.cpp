@@ -1246,6 +1246,43 @@ template <typename R> void QInterface<R>::GetReducedDensityMatrix(bitLenInt q, c
     out[3] = cplx<R>((R)r11, 0);
 }
 
+template <typename R>
+void QInterface<R>::GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out)
+{
+    validateRdmQubits(qubits, qubitCount);
+    if (qubitCount > 26u) throw QrackError("GetReducedDensityMatrix: dense fallback width cap");
+    std::vector<cplx<R>> sv(maxQPower);
+    GetQuantumState(sv.data());
+    const size_t D = (size_t)1 << qubits.size();
+    const std::vector<bitCapInt> off = rdmKeptOffsets(qubits);
+    const std::vector<bitCapInt> pows = rdmKeptPowers(qubits);
+    std::vector<double> re(D * D, 0.0), im(D * D, 0.0);
+    std::vector<cplx<R>> row(D);
+    // one gather per environment index, upper triangle only
+    const bitCapInt nEnv = maxQPower >> qubits.size();
+    for (bitCapInt e = 0; e < nEnv; ++e) {
+        bitCapInt i = e;
+        for (bitCapInt p : pows) i = insertZeroBit(i, p);
+        for (size_t a = 0; a < D; ++a) row[a] = sv[i | off[a]];
+        for (size_t a = 0; a < D; ++a) {
+            const cplx<R> x = row[a];
+            re[a * D + a] += (double)(x.re * x.re + x.im * x.im);
+            for (size_t b = a + 1; b < D; ++b) {
+                const cplx<R> y = row[b];
+                re[a * D + b] += (double)(x.re * y.re + x.im * y.im);
+                im[a * D + b] += (double)(x.im * y.re - x.re * y.im);
+            }
+        }
+    }
+    for (size_t a = 0; a < D; ++a) {
+        out[a * D + a] = cplx<double>(re[a * D + a], 0.0);
+        for (size_t b = a + 1; b < D; ++b) {
+            out[a * D + b] = cplx<double>(re[a * D + b], im[a * D + b]);
+            out[b * D + a] = cplx<double>(re[a * D + b], -im[a * D + b]);
+        }
+    }
+}
+
 template class QInterface<float>;
 template class QInterface<double>;
 

@@ -13,6 +13,7 @@
 #include "common/rng.hpp"
 #include "common/types.hpp"
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <vector>
@@ -44,6 +45,46 @@ inline void validatePauliTerms(const std::vector<PauliTerm>& terms, bitLenInt qu
             }
         }
     }
+}
+
+// most qubits a reduced density matrix may keep (a 4096 x 4096 result)
+constexpr int QA_RDM_MAX_QUBITS = 12;
+
+// Kept-qubit argument check of GetReducedDensityMatrix, shared by every
+// implementation
+inline void validateRdmQubits(const std::vector<bitLenInt>& qubits, bitLenInt qubitCount)
+{
+    const std::string w("GetReducedDensityMatrix");
+    if (qubits.empty()) throw QrackError(w + ": no qubits");
+    if (qubits.size() > (size_t)QA_RDM_MAX_QUBITS) throw QrackError(w + ": more than 12 kept qubits");
+    for (size_t i = 0; i < qubits.size(); ++i) {
+        if (qubits[i] >= qubitCount) throw QrackError(w + ": qubit out of range");
+        for (size_t j = 0; j < i; ++j) {
+            if (qubits[j] == qubits[i]) throw QrackError(w + ": qubit repeated");
+        }
+    }
+}
+
+// offset of kept index a in the state: bit j of a goes to qubits[j]
+inline std::vector<bitCapInt> rdmKeptOffsets(const std::vector<bitLenInt>& qubits)
+{
+    std::vector<bitCapInt> off((size_t)1 << qubits.size(), 0);
+    for (size_t a = 0; a < off.size(); ++a) {
+        for (size_t j = 0; j < qubits.size(); ++j) {
+            if ((a >> j) & 1u) off[a] |= pow2(qubits[j]);
+        }
+    }
+    return off;
+}
+
+// powers of the kept qubits, ascending: what insertZeroBit walks to turn an
+// environment index into a state index
+inline std::vector<bitCapInt> rdmKeptPowers(const std::vector<bitLenInt>& qubits)
+{
+    std::vector<bitCapInt> pows;
+    for (bitLenInt q : qubits) pows.push_back(pow2(q));
+    std::sort(pows.begin(), pows.end());
+    return pows;
 }
 
 template <typename R> class QInterface;
@@ -1113,6 +1154,12 @@ public:
     // single-qubit reduced density matrix (parity: qinterface.cpp:885
     // GetReducedDensityMatrix); out = row-major 2x2
     virtual void GetReducedDensityMatrix(bitLenInt q, cplx<R>* out);
+    // reduced density matrix of `qubits` (parity: qinterface.hpp
+    // GetReducedDensityMatrix(qubits, out)); out = row-major D x D doubles,
+    // D = 2^k, bit j of a row / column index is the value of qubits[j]:
+    // rho[a,b] = sum_env psi[env,a] conj(psi[env,b]). Engines override with a
+    // read-only pass; the default lowering copies the state to the host.
+    virtual void GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out);
 };
 
 } // namespace qrack_amd

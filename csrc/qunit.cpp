@@ -1216,6 +1216,54 @@ bitCapInt QUnit<R>::IndexedLDA(bitLenInt indexStart, bitLenInt indexLength, bitL
         ->IndexedLDA(0, indexLength, indexLength, valueLength, values, resetValue);
 }
 
+// Distinct units are in a product state, so the matrix of a kept set is the
+// Kronecker product of each unit's matrix over its own kept qubits.
+template <typename R>
+void QUnit<R>::GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out)
+{
+    validateRdmQubits(qubits, qubitCount);
+    for (bitLenInt q : qubits) FlushPhasePairs(q);
+    struct Group {
+        QInterfacePtr<R> unit;
+        std::vector<bitLenInt> mapped;
+        std::vector<size_t> pos; // position of each mapped qubit in the caller's list
+        std::vector<cplx<double>> rho;
+    };
+    std::vector<Group> groups;
+    for (size_t j = 0; j < qubits.size(); ++j) {
+        const auto& sh = shards[qubits[j]];
+        size_t g = 0;
+        while (g < groups.size() && groups[g].unit != sh.unit) ++g;
+        if (g == groups.size()) groups.push_back(Group{ sh.unit, {}, {}, {} });
+        groups[g].mapped.push_back(sh.mapped);
+        groups[g].pos.push_back(j);
+    }
+    for (Group& g : groups) {
+        g.rho.resize((size_t)1 << (2u * g.mapped.size()));
+        g.unit->GetReducedDensityMatrix(g.mapped, g.rho.data());
+    }
+    const size_t D = (size_t)1 << qubits.size();
+    // sub[g][a]: the unit-local index that caller index a selects in group g
+    std::vector<std::vector<size_t>> sub(groups.size(), std::vector<size_t>(D, 0));
+    for (size_t g = 0; g < groups.size(); ++g) {
+        for (size_t a = 0; a < D; ++a) {
+            for (size_t m = 0; m < groups[g].pos.size(); ++m) {
+                sub[g][a] |= ((a >> groups[g].pos[m]) & 1u) << m;
+            }
+        }
+    }
+    for (size_t a = 0; a < D; ++a) {
+        for (size_t b = 0; b < D; ++b) {
+            cplx<double> v(1.0, 0.0);
+            for (size_t g = 0; g < groups.size(); ++g) {
+                const size_t Dg = (size_t)1 << groups[g].mapped.size();
+                v = v * groups[g].rho[sub[g][a] * Dg + sub[g][b]];
+            }
+            out[a * D + b] = v;
+        }
+    }
+}
+
 template class QUnit<float>;
 template class QUnit<double>;
 

@@ -645,6 +645,7 @@ public:
         FlushPhasePairs(q);
         shards[q].unit->GetReducedDensityMatrix(shards[q].mapped, out);
     }
+    void GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out) override;
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override;

@@ -153,6 +153,14 @@ public:
     {
         return inner->ExpectationPauliSum(t);
     }
+    void GetReducedDensityMatrix(bitLenInt q, cplx<R>* out) override
+    {
+        inner->GetReducedDensityMatrix(q, out);
+    }
+    void GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits, cplx<double>* out) override
+    {
+        inner->GetReducedDensityMatrix(qubits, out);
+    }
     void PauliRotation(
         const std::vector<bitLenInt>& b, const std::vector<Pauli>& p, double theta) override
     {

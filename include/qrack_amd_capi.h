@@ -90,6 +90,10 @@ double qrack_joint_ensemble_probability(quid sid, const int* paulis, const uint6
  * (Pauli codes 0=I 1=X 2=Z 3=Y) */
 double qrack_expectation_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
     const uint64_t* termLens, const uint64_t* qs, const int* paulis);
+/* reduced density matrix of the n listed qubits (n <= 12): rho receives
+ * 2 * 4^n doubles, row-major (re, im) pairs; bit j of a row or column index
+ * is the value of qs[j] */
+void qrack_reduced_density_matrix(quid sid, const uint64_t* qs, uint64_t n, double* rho);
 /* exp(-i theta P), global phase included, P the product of the listed Paulis
  * (so a lone Z is RZ(2 theta)); an all-identity string is the phase e^{-i theta} */
 void qrack_pauli_rotation(quid sid, const int* paulis, const uint64_t* qs, uint64_t n, double theta);

@@ -25,6 +25,11 @@ from qrack_amd._qrack import (  # noqa: F401
     profile_reset,
     qft_pass_plan,
     pauli_evolve_plan,
+    rdm_pass_plan,
+    RDM_MAX_QUBITS,
+    RDM_REG_MAX,
+    RDM_TILE_MAX,
+    RDM_RUN,
     save_stabilizer_F,
     save_stabilizer_D,
     load_stabilizer_F,
@@ -42,6 +47,26 @@ Pauli_I, Pauli_X, Pauli_Z, Pauli_Y = 0, 1, 2, 3
 # Pauli-sum terms sharing one X/Y mask that the HIP engine serves per launch
 # (0 when the extension was built without the HIP engine)
 PAULI_MAX_TERMS = getattr(_qrack, "PAULI_MAX_TERMS", 0)
+
+
+def purity(sim, qubits):
+    """Tr rho^2 of the reduced density matrix of `qubits`."""
+    rho = sim.reduced_density_matrix(list(qubits))
+    # Tr rho^2 = sum |rho_ab|^2 for a Hermitian rho
+    return float((rho.real**2 + rho.imag**2).sum())
+
+
+def entanglement_entropy(sim, qubits, base=2.0):
+    """Von Neumann entropy -Tr rho log rho of the reduced density matrix of
+    `qubits`, in units of log `base` (bits by default)."""
+    import math
+
+    import numpy as np
+
+    rho = sim.reduced_density_matrix(list(qubits))
+    ev = np.clip(np.linalg.eigvalsh(rho), 0.0, None)
+    ev = ev[ev > 0.0]  # 0 log 0 = 0
+    return float(-(ev * np.log(ev)).sum() / math.log(base))
 
 
 def create_simulator(
