@@ -21,6 +21,7 @@
 #ifdef QRACK_AMD_HIP_ENGINE
 #include "hip/qengine_hip.hpp"
 #endif
+#include "hip/mtrxn_plan.hpp"
 #include "hip/qft_plan.hpp"
 #include "hip/rdm_plan.hpp"
 
@@ -100,6 +101,36 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
                 for (int i = 0; i < 16; ++i) mm[i] = from_std<R>(m[i]);
                 q.Mtrx2q(mm.data(), a, b);
             })
+        .def(
+            "mtrx_n",
+            [](QI& q, std::vector<long> qubits,
+                py::array_t<C, py::array::c_style | py::array::forcecast> matrix,
+                std::vector<long> controls, bool anti) {
+                if (qubits.empty() || qubits.size() > (size_t)QA_MTRXN_MAX) {
+                    throw QrackError("mtrx_n: need 1 to 6 target qubits");
+                }
+                std::vector<bitLenInt> qs, cs;
+                for (long b : qubits) {
+                    if (b < 0 || b >= (long)q.GetQubitCount()) throw QrackError("mtrx_n: qubit out of range");
+                    qs.push_back((bitLenInt)b);
+                }
+                for (long b : controls) {
+                    if (b < 0 || b >= (long)q.GetQubitCount()) throw QrackError("mtrx_n: control out of range");
+                    cs.push_back((bitLenInt)b);
+                }
+                const py::ssize_t D = (py::ssize_t)1 << qs.size();
+                const bool flat = matrix.ndim() == 1 && matrix.shape(0) == D * D;
+                const bool square = matrix.ndim() == 2 && matrix.shape(0) == D && matrix.shape(1) == D;
+                if (!flat && !square) throw QrackError("mtrx_n: need a 2^k x 2^k matrix, 4^k entries");
+                std::vector<cplx<R>> mm((size_t)(D * D));
+                for (py::ssize_t i = 0; i < D * D; ++i) mm[(size_t)i] = from_std<R>(matrix.data()[i]);
+                q.MtrxN(qs, mm.data(), cs, anti);
+            },
+            py::arg("qubits"), py::arg("matrix"), py::arg("controls") = std::vector<long>(),
+            py::arg("anti") = false,
+            "dense k-qubit gate, k <= MTRXN_MAX: matrix is 4^k complex numbers, flat row-major or "
+            "(2^k, 2^k); bit g of a row or column index is the value of qubits[g]; controls (all "
+            "set, or all clear with anti) select the subspace. Applied as given")
         .def("mtrx_2q_batch",
             [](QI& q, std::vector<C> ms, std::vector<bitLenInt> q1s, std::vector<bitLenInt> q2s) {
                 std::vector<cplx<R>> mm(ms.size());
@@ -982,6 +1013,51 @@ PYBIND11_MODULE(_qrack, m)
         "launches the HIP engine walks for reduced_density_matrix(qubits): the regime "
         "(\"register\" | \"tile\" | \"wide\"), the kept qubits a launch resolves itself, those the "
         "launch list enumerates, and the (row, column) block values of every launch");
+    // the HIP engine's layout of a dense k-qubit gate; needs no GPU
+    m.def(
+        "mtrx_n_plan",
+        [](int n, std::vector<long> qubits, std::vector<long> controls, const std::string& precision,
+            bool anti, bool check) {
+            if (precision != "fp32" && precision != "fp64") {
+                throw std::invalid_argument("mtrx_n_plan: precision must be fp32 or fp64");
+            }
+            if (n < 1 || n > 62) throw std::invalid_argument("mtrx_n_plan: need 1 <= n <= 62");
+            std::vector<bitLenInt> qs, cs;
+            for (long b : qubits) {
+                if (b < 0 || b >= n) throw QrackError("mtrx_n_plan: qubit out of range");
+                qs.push_back((bitLenInt)b);
+            }
+            for (long b : controls) {
+                if (b < 0 || b >= n) throw QrackError("mtrx_n_plan: control out of range");
+                cs.push_back((bitLenInt)b);
+            }
+            validateMtrxN(qs, cs, (bitLenInt)n);
+            const std::vector<int> qi(qubits.begin(), qubits.end()), ci(controls.begin(), controls.end());
+            const MtrxNPlan p = mtrxnPlan(n, qi, ci, anti, precision == "fp32" ? 4 : 8);
+            py::dict d;
+            d["route"] = mtrxnRouteName(p.route);
+            d["tile_bits"] = p.tileBits;
+            d["run_bits"] = p.geom.run;
+            d["tiles"] = p.geom.nTiles;
+            d["orbits_per_tile"] = p.orbitsPerTile;
+            d["rows_per_thread"] = p.rowsPerThread;
+            d["matrix_in"] = p.matrixInKernarg ? "kernarg" : "aux";
+            d["controls_out_of_tile"] = p.cHigh;
+            d["target_order"] = p.order;
+            if (check) {
+                if (n > 20) throw std::invalid_argument("mtrx_n_plan: check walks 2^n indices, n <= 20");
+                d["covers"] = mtrxnPlanCovers(p, n, ci, anti);
+            }
+            return d;
+        },
+        py::arg("n"), py::arg("qubits"), py::arg("controls") = std::vector<long>(),
+        py::arg("precision") = "fp32", py::arg("anti") = false, py::arg("check") = false,
+        "how the HIP engine lays out mtrx_n(qubits, ., controls) on n qubits: the route "
+        "(\"apply2x2\" | \"mtrx_2q\" | \"mtrx_n\"), the bits of the LDS tile, the length of its "
+        "contiguous run, the tiles visited, orbits per tile, rows per thread and where the matrix "
+        "travels (\"kernarg\" | \"aux\"). check=True also walks every index the kernel would touch "
+        "and reports under \"covers\" whether they are exactly the amplitudes to visit");
+    m.attr("MTRXN_MAX") = (int)QA_MTRXN_MAX;
     m.attr("RDM_MAX_QUBITS") = (int)QA_RDM_MAX_QUBITS;
     m.attr("RDM_REG_MAX") = (int)QA_RDM_REG_MAX;
     m.attr("RDM_TILE_MAX") = (int)QA_RDM_TILE_MAX;

@@ -570,6 +570,31 @@ void qrack_reduced_density_matrix(quid sid, const uint64_t* qs, uint64_t n, doub
     });
 }
 
+void qrack_mtrx_n(quid sid, uint64_t k, const uint64_t* qs, const double* m, uint64_t nc,
+    const uint64_t* controls, int anti)
+{
+    guarded(sid, [&](SimSlot& s) {
+        if (k < 1 || k > (uint64_t)QA_MTRXN_MAX) throw QrackError("qrack_mtrx_n: need 1 <= k <= 6");
+        for (uint64_t i = 0; i < k; ++i) {
+            if (qs[i] >= s.Qubits()) throw QrackError("qrack_mtrx_n: qubit out of range");
+        }
+        for (uint64_t i = 0; i < nc; ++i) {
+            if (controls[i] >= s.Qubits()) throw QrackError("qrack_mtrx_n: control out of range");
+        }
+        const std::vector<bitLenInt> qv = ctrlVec(qs, k), cv = ctrlVec(controls, nc);
+        const size_t len = (size_t)1 << (2u * k);
+        if (s.f) {
+            std::vector<cplx<float>> mm(len);
+            for (size_t i = 0; i < len; ++i) mm[i] = cplx<float>((float)m[2 * i], (float)m[2 * i + 1]);
+            s.f->MtrxN(qv, mm.data(), cv, anti != 0);
+        } else if (s.d) {
+            std::vector<cplx<double>> mm(len);
+            for (size_t i = 0; i < len; ++i) mm[i] = cplx<double>(m[2 * i], m[2 * i + 1]);
+            s.d->MtrxN(qv, mm.data(), cv, anti != 0);
+        }
+    });
+}
+
 void qrack_pauli_rotation(
     quid sid, const int* paulis, const uint64_t* qs, uint64_t n, double theta)
 {

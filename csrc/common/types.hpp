@@ -27,6 +27,9 @@ typedef uint64_t bitCapInt;  // amplitude index / bit mask
 
 constexpr bitCapInt ONE_BCI = 1u;
 
+// widest dense gate MtrxN applies (a 64 x 64 matrix)
+constexpr int QA_MTRXN_MAX = 6;
+
 // NOTE: indices are 64-bit; layers that hold factorized/compressed states
 // (QUnit, QStabilizer, sparse) support MORE than 63 qubits as long as any
 // single dense mask stays under 64 bits. pow2 saturates (all-ones) past

@@ -4184,4 +4184,174 @@ void launchRdmTile(const cplx<R>* sv, int kt, const RdmTileArgs& a, double* part
 QA_INSTANTIATE(float)
 QA_INSTANTIATE(double)
 
+// ---- dense k-qubit gate: one tiled pass -------------------------------------
+// Defined and instantiated after the list above, so that the kernels of that
+// list keep their order in the code object.
+
+__device__ __forceinline__ float mtrxnFma1(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double mtrxnFma1(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// acc += m * x as four fused multiply-adds
+template <typename R> __device__ __forceinline__ void mtrxnFma(cplx<R>& acc, cplx<R> m, cplx<R> x)
+{
+    acc.re = mtrxnFma1(m.re, x.re, acc.re);
+    acc.im = mtrxnFma1(m.re, x.im, acc.im);
+    acc.re = mtrxnFma1(-m.im, x.im, acc.re);
+    acc.im = mtrxnFma1(m.im, x.re, acc.im);
+}
+
+// RPT output rows of one orbit: the orbit's 2^K inputs stream from LDS once
+// for all of them. UNI: the row block is the same for the whole wave (the tile
+// holds at least 64 orbits), so the matrix entries are scalar loads; two
+// columns a trip keep them within the scalar registers. Otherwise they are
+// vector loads, one column a trip.
+template <typename R, int K, int RPT, bool UNI>
+__device__ __forceinline__ void mtrxnRows(const cplx<R>* tile, const cplx<R>* __restrict__ dm,
+    int oBits, unsigned o, unsigned rb, cplx<R>* acc)
+{
+    constexpr int D = 1 << K;
+    constexpr int CU = UNI ? 2 : 1;
+    if constexpr (UNI) rb = (unsigned)__builtin_amdgcn_readfirstlane((int)rb);
+    const cplx<R>* __restrict__ rows = dm + (size_t)rb * RPT * D;
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) acc[i] = cplx<R>(0, 0);
+#pragma unroll 1
+    for (int c0 = 0; c0 < D; c0 += CU) {
+        cplx<R> x[CU];
+#pragma unroll
+        for (int u = 0; u < CU; ++u) x[u] = tile[mtrxnSlot(K, oBits, (unsigned)(c0 + u), o)];
+#pragma unroll
+        for (int i = 0; i < RPT; ++i) {
+#pragma unroll
+            for (int u = 0; u < CU; ++u) mtrxnFma(acc[i], rows[i * D + c0 + u], x[u]);
+        }
+    }
+}
+
+// A workgroup strides over its tiles (mtrxn_plan.hpp): stage the tile with
+// 16-byte global accesses, mat-vec every orbit that passes the in-tile
+// controls, store the tile back. With up to 2^(TB-8) rows a thread owns whole
+// orbits and works in registers; above, 2^K / RPT threads share an orbit, keep
+// their accumulators across a barrier and write them to the slots they read.
+// A smaller state leaves threads idle in the same code.
+template <typename R, int K>
+__global__ __launch_bounds__(QA_MTRXN_BLOCK) void k_mtrx_n(
+    cplx<R>* __restrict__ sv, const cplx<R>* __restrict__ dm, const MtrxNArgs<R> a)
+{
+    constexpr int TB = qaLdsTileBits<R>();
+    constexpr int D = 1 << K;
+    constexpr int RPT = mtrxnRowsPerThread(K, TB);
+    constexpr int G = D / RPT;
+    constexpr unsigned VEC = sizeof(R) == 4 ? 2 : 1; // amplitudes per 16-byte access
+    constexpr unsigned STEP = QA_MTRXN_BLOCK * VEC;
+    static_assert(G == 1 || G * (1 << (TB - K)) <= QA_MTRXN_BLOCK, "one work item per thread");
+    __shared__ cplx<R> tile[1u << TB];
+    const MtrxNGeom& g = a.g;
+    const unsigned tileLen = 1u << g.m;
+    const int oBits = g.m - K;
+    const unsigned nOrb = 1u << oBits;
+    const unsigned tid = threadIdx.x;
+    // the staging maps are linear over XOR: thread part here, trip part (wave
+    // uniform) in the loop
+    const unsigned lLo = tid * VEC;
+    const unsigned slotLo = mtrxnLdsAddr(g, lLo);
+    const bitCapInt offLo = mtrxnGlobalOff(g, lLo);
+    const unsigned slot1 = mtrxnLdsAddr(g, 1u);
+    const cplx<R>* __restrict__ mp = K <= 3 ? a.m : dm;
+
+    for (bitCapInt t = blockIdx.x; t < g.nTiles; t += gridDim.x) {
+        cplx<R>* base = sv + mtrxnTileBase(g, t);
+        for (unsigned lHi = 0; lHi < tileLen; lHi += STEP) {
+            if ((lHi | lLo) >= tileLen) continue;
+            const unsigned s = slotLo ^ mtrxnLdsAddr(g, lHi);
+            const bitCapInt off = offLo | mtrxnGlobalOff(g, lHi);
+            if constexpr (VEC == 2) {
+                const float4 v = *reinterpret_cast<const float4*>(base + off);
+                tile[s] = cplx<R>(v.x, v.y);
+                tile[s ^ slot1] = cplx<R>(v.z, v.w);
+            } else {
+                tile[s] = base[off];
+            }
+        }
+        __syncthreads();
+
+        if constexpr (G == 1) {
+            for (unsigned o = tid; o < nOrb; o += QA_MTRXN_BLOCK) {
+                if ((o & g.cMaskO) != g.cValO) continue;
+                cplx<R> v[D];
+#pragma unroll
+                for (int c = 0; c < D; ++c) v[c] = tile[mtrxnSlot(K, oBits, (unsigned)c, o)];
+                // rows stay a loop from 8 x 8 on: unrolled, the whole matrix
+                // is hoisted into scalar registers and spills
+#pragma unroll(D >= 8 ? 2 : D)
+                for (int r = 0; r < D; ++r) {
+                    cplx<R> acc(0, 0);
+#pragma unroll
+                    for (int c = 0; c < D; ++c) mtrxnFma(acc, mp[r * D + c], v[c]);
+                    tile[mtrxnSlot(K, oBits, (unsigned)r, o)] = acc;
+                }
+            }
+            __syncthreads();
+        } else {
+            const unsigned o = tid & (nOrb - 1u);
+            const unsigned rb = tid >> oBits;
+            const bool active = rb < (unsigned)G && (o & g.cMaskO) == g.cValO;
+            cplx<R> acc[RPT];
+            if (active) {
+                if (nOrb >= 64u) {
+                    mtrxnRows<R, K, RPT, true>(tile, mp, oBits, o, rb, acc);
+                } else {
+                    mtrxnRows<R, K, RPT, false>(tile, mp, oBits, o, rb, acc);
+                }
+            }
+            __syncthreads();
+            if (active) {
+#pragma unroll
+                for (int i = 0; i < RPT; ++i) {
+                    tile[mtrxnSlot(K, oBits, rb * RPT + (unsigned)i, o)] = acc[i];
+                }
+            }
+            __syncthreads();
+        }
+
+        for (unsigned lHi = 0; lHi < tileLen; lHi += STEP) {
+            if ((lHi | lLo) >= tileLen) continue;
+            const unsigned s = slotLo ^ mtrxnLdsAddr(g, lHi);
+            const bitCapInt off = offLo | mtrxnGlobalOff(g, lHi);
+            if constexpr (VEC == 2) {
+                const cplx<R> x = tile[s], y = tile[s ^ slot1];
+                *reinterpret_cast<float4*>(base + off) = make_float4(x.re, x.im, y.re, y.im);
+            } else {
+                base[off] = tile[s];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <typename R, int K>
+static void launchMtrxNK(cplx<R>* sv, const cplx<R>* dm, const MtrxNArgs<R>& a, hipStream_t stream)
+{
+    const int grid = ldsGridFor(a.g.nTiles);
+    hipLaunchKernelGGL(
+        (k_mtrx_n<R, K>), dim3(grid), dim3(QA_MTRXN_BLOCK), 0, stream, sv, dm, a);
+}
+
+template <typename R>
+void launchMtrxN(cplx<R>* sv, const cplx<R>* dm, const MtrxNArgs<R>& a, hipStream_t stream)
+{
+    switch (a.g.k) {
+    case 1: launchMtrxNK<R, 1>(sv, dm, a, stream); break;
+    case 2: launchMtrxNK<R, 2>(sv, dm, a, stream); break;
+    case 3: launchMtrxNK<R, 3>(sv, dm, a, stream); break;
+    case 4: launchMtrxNK<R, 4>(sv, dm, a, stream); break;
+    case 5: launchMtrxNK<R, 5>(sv, dm, a, stream); break;
+    default: launchMtrxNK<R, 6>(sv, dm, a, stream); break;
+    }
+}
+
+template void launchMtrxN<float>(cplx<float>*, const cplx<float>*, const MtrxNArgs<float>&, hipStream_t);
+template void launchMtrxN<double>(
+    cplx<double>*, const cplx<double>*, const MtrxNArgs<double>&, hipStream_t);
+
 } // namespace qrack_amd

@@ -10,6 +10,7 @@
 #pragma once
 
 #include "../common/types.hpp"
+#include "mtrxn_plan.hpp"
 #include "rdm_plan.hpp"
 
 #include <hip/hip_runtime.h>
@@ -453,6 +454,19 @@ template <typename R> struct Gate4x4Args {
 
 template <typename R>
 void launchMtrx2q(cplx<R>* sv, const Gate4x4Args<R>& a, hipStream_t stream);
+
+// dense k-qubit gate, 1 <= k <= QA_MTRXN_MAX, any targets, controls or
+// anti-controls: ONE read-modify-write pass through an LDS tile whose address
+// bits are the targets plus the lowest other bits (mtrxn_plan.hpp). The matrix
+// is in the basis of the ascending targets; k <= 3 reads it from `m` in the
+// kernel arguments, k >= 4 from `dm` (device memory, 4^k entries).
+template <typename R> struct MtrxNArgs {
+    MtrxNGeom g;
+    cplx<R> m[64];
+};
+
+template <typename R>
+void launchMtrxN(cplx<R>* sv, const cplx<R>* dm, const MtrxNArgs<R>& a, hipStream_t stream);
 
 // TWO disjoint 4x4s in ONE full-state pass (16-amplitude orbits — the same
 // register-orbit budget the 4-column QFT kernel proved runs at full HBM

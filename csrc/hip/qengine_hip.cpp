@@ -575,6 +575,49 @@ void QEngineHIP<R>::Mtrx2q(const cplx<R>* m, bitLenInt q1, bitLenInt q2)
     launchMtrx2q<R>(wState(), a, stream);
 }
 
+// dense k-qubit gate. The kernel works on the targets in ascending order, so
+// the matrix's rows and columns are permuted to match on the host (no
+// arithmetic). Up to 8 x 8 it travels in the kernel arguments, above that
+// through the engine's aux buffer.
+template <typename R>
+void QEngineHIP<R>::MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+    const std::vector<bitLenInt>& controls, bool anti)
+{
+    validateMtrxN(qubits, controls, qubitCount);
+    const MtrxNPlan plan = mtrxnPlan((int)qubitCount, std::vector<int>(qubits.begin(), qubits.end()),
+        std::vector<int>(controls.begin(), controls.end()), anti, (int)sizeof(R));
+    if (plan.route == MtrxNRoute::Apply2x2) {
+        if (controls.empty()) {
+            this->Mtrx(mtrx, qubits[0]);
+        } else if (anti) {
+            this->MACMtrx(controls, mtrx, qubits[0]);
+        } else {
+            this->MCMtrx(controls, mtrx, qubits[0]);
+        }
+        return;
+    }
+    if (plan.route == MtrxNRoute::Mtrx2q) {
+        this->Mtrx2q(mtrx, qubits[0], qubits[1]);
+        return;
+    }
+    const size_t D = (size_t)1 << qubits.size();
+    MtrxNArgs<R> a{};
+    a.g = plan.geom;
+    const cplx<R>* dm = nullptr;
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    if (plan.matrixInKernarg) {
+        mtrxnPermuteMatrix(plan, mtrx, a.m);
+    } else {
+        QA_HIP_CHECK(hipStreamSynchronize(stream)); // hAux_ and dAux_ are free again
+        hAux_.resize(sizeof(cplx<R>) * D * D);
+        mtrxnPermuteMatrix(plan, mtrx, reinterpret_cast<cplx<R>*>(hAux_.data()));
+        dm = reinterpret_cast<const cplx<R>*>(uploadAux(sizeof(cplx<R>) * D * D));
+    }
+    HipProfScope prof("mtrx_n", stream);
+    launchMtrxN<R>(wState(), dm, a, stream);
+    runningNorm = (R)-1;
+}
+
 // batched disjoint two-qubit 4x4 layer: in-tile pairs fuse through the LDS
 // kernel; the rest apply as single-pass 4x4s.
 template <typename R>

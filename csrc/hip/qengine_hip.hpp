@@ -136,6 +136,11 @@ public:
     void Mtrx2q(const cplx<R>* m16, bitLenInt q1, bitLenInt q2) override;
     void Mtrx2qBatch(const std::vector<cplx<R>>& ms, const std::vector<bitLenInt>& q1s,
         const std::vector<bitLenInt>& q2s) override;
+    // dense k-qubit gate: one tiled pass (k_mtrx_n) laid out by mtrxnPlan
+    // (mtrxn_plan.hpp); k = 1 and the uncontrolled k = 2 go to the kernels
+    // that already serve them
+    void MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+        const std::vector<bitLenInt>& controls = {}, bool anti = false) override;
     void ApplyM(bitCapInt regMask, bitCapInt result, cplx<R> nrm) override;
     void GetAmplitudePage(cplx<R>* pagePtr, bitCapInt offset, bitCapInt length) override;
     void SetAmplitudePage(const cplx<R>* pagePtr, bitCapInt offset, bitCapInt length) override;

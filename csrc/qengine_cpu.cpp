@@ -150,6 +150,48 @@ void QEngineCPU<R>::Mtrx2q(const cplx<R>* m, bitLenInt q1, bitLenInt q2)
     });
 }
 
+// dense k-qubit gate: gather the orbit's 2^k amplitudes, mat-vec, scatter;
+// orbits outside the control subspace are never visited
+template <typename R>
+void QEngineCPU<R>::MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+    const std::vector<bitLenInt>& controls, bool anti)
+{
+    validateMtrxN(qubits, controls, qubitCount);
+    const int D = 1 << qubits.size();
+    std::vector<cplx<R>> mm(mtrx, mtrx + (size_t)D * D);
+    std::vector<bitCapInt> off((size_t)D, 0);
+    for (int a = 0; a < D; ++a) {
+        for (size_t g = 0; g < qubits.size(); ++g) {
+            if ((a >> g) & 1) off[a] |= pow2(qubits[g]);
+        }
+    }
+    std::vector<bitCapInt> pows;
+    bitCapInt cMask = 0;
+    for (bitLenInt q : qubits) pows.push_back(pow2(q));
+    for (bitLenInt c : controls) {
+        pows.push_back(pow2(c));
+        cMask |= pow2(c);
+    }
+    std::sort(pows.begin(), pows.end());
+    const bitCapInt cVal = anti ? 0 : cMask;
+    cplx<R>* sv = stateVec.data();
+    const cplx<R>* m = mm.data();
+    const bitCapInt* offs = off.data();
+    this->par_for_mask(maxQPower >> (bitLenInt)pows.size(), pows,
+        [sv, m, offs, D, cVal](const bitCapInt& i0, unsigned) {
+            const bitCapInt i = i0 | cVal;
+            cplx<R> v[1 << QA_MTRXN_MAX];
+            for (int a = 0; a < D; ++a) v[a] = sv[i | offs[a]];
+            for (int r = 0; r < D; ++r) {
+                const cplx<R>* row = m + (size_t)r * D;
+                cplx<R> acc = row[0] * v[0];
+                for (int c = 1; c < D; ++c) acc = acc + row[c] * v[c];
+                sv[i | offs[r]] = acc;
+            }
+        });
+    runningNorm = (R)-1;
+}
+
 // batched controlled-phase pairs: one diagonal pass for a whole layer
 template <typename R>
 void QEngineCPU<R>::CPhasePairs(const std::vector<bitLenInt>& controls,

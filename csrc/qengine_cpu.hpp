@@ -65,6 +65,9 @@ public:
     void CPhasePairs(const std::vector<bitLenInt>& controls, const std::vector<bitLenInt>& targets,
         const std::vector<double>& angles) override;
     void Mtrx2q(const cplx<R>* m16, bitLenInt q1, bitLenInt q2) override;
+    // dense k-qubit gate: one sweep over the orbits of the control subspace
+    void MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+        const std::vector<bitLenInt>& controls = {}, bool anti = false) override;
     void QftColumnGeneral(bitLenInt target, double scale, bitLenInt rampStart,
         bitCapInt inPlaceRelMask, const std::vector<bitCapInt>& sPows,
         const std::vector<uint64_t>& sWeights, double phase0, bool pre) override;

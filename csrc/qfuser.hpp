@@ -470,6 +470,13 @@ public:
         for (size_t i = 0; i < targets.size(); ++i) Mtrx(&mtrxs[4u * i], targets[i]);
     }
     void Mtrx2q(const cplx<R>* m16, bitLenInt q1, bitLenInt q2) override { Queue2q(m16, q1, q2); }
+    // a dense k-qubit gate is not queued: pending work goes first
+    void MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+        const std::vector<bitLenInt>& controls = {}, bool anti = false) override
+    {
+        FlushAll();
+        inner->MtrxN(qubits, mtrx, controls, anti);
+    }
     void Mtrx2qBatch(const std::vector<cplx<R>>& ms, const std::vector<bitLenInt>& q1s,
         const std::vector<bitLenInt>& q2s) override
     {

@@ -1283,6 +1283,19 @@ void QInterface<R>::GetReducedDensityMatrix(const std::vector<bitLenInt>& qubits
     }
 }
 
+template <typename R>
+void QInterface<R>::MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+    const std::vector<bitLenInt>& controls, bool anti)
+{
+    validateMtrxN(qubits, controls, qubitCount);
+    if (qubitCount > 26u) throw QrackError("MtrxN: dense fallback width cap");
+    std::vector<cplx<R>> sv(maxQPower);
+    GetQuantumState(sv.data());
+    mtrxNHostApply<R>(sv.data(), qubits, mtrx, controls, anti, 0,
+        maxQPower >> (bitLenInt)(qubits.size() + controls.size()));
+    SetQuantumState(sv.data());
+}
+
 template class QInterface<float>;
 template class QInterface<double>;
 

@@ -87,6 +87,69 @@ inline std::vector<bitCapInt> rdmKeptPowers(const std::vector<bitLenInt>& qubits
     return pows;
 }
 
+// Argument check of MtrxN, shared by every implementation
+inline void validateMtrxN(const std::vector<bitLenInt>& qubits, const std::vector<bitLenInt>& controls,
+    bitLenInt qubitCount)
+{
+    const std::string w("MtrxN");
+    if (qubits.empty()) throw QrackError(w + ": no target qubits");
+    if (qubits.size() > (size_t)QA_MTRXN_MAX) throw QrackError(w + ": more than 6 target qubits");
+    for (size_t i = 0; i < qubits.size(); ++i) {
+        if (qubits[i] >= qubitCount) throw QrackError(w + ": qubit out of range");
+        for (size_t j = 0; j < i; ++j) {
+            if (qubits[j] == qubits[i]) throw QrackError(w + ": qubit repeated");
+        }
+    }
+    for (size_t i = 0; i < controls.size(); ++i) {
+        if (controls[i] >= qubitCount) throw QrackError(w + ": control out of range");
+        for (size_t j = 0; j < i; ++j) {
+            if (controls[j] == controls[i]) throw QrackError(w + ": control repeated");
+        }
+        for (bitLenInt q : qubits) {
+            if (q == controls[i]) throw QrackError(w + ": control is also a target");
+        }
+    }
+}
+
+// MtrxN on a host state vector, orbits [first, last) of the 2^(n-k-c) the
+// control subspace holds: gather 2^k amplitudes, mat-vec, scatter. Bit g of a
+// row or column index is the value of qubits[g]. The default lowering runs it
+// over a host copy of the state.
+template <typename R>
+inline void mtrxNHostApply(cplx<R>* sv, const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+    const std::vector<bitLenInt>& controls, bool anti, bitCapInt first, bitCapInt last)
+{
+    const size_t D = (size_t)1 << qubits.size();
+    std::vector<bitCapInt> off(D, 0);
+    for (size_t a = 0; a < D; ++a) {
+        for (size_t g = 0; g < qubits.size(); ++g) {
+            if ((a >> g) & 1u) off[a] |= pow2(qubits[g]);
+        }
+    }
+    std::vector<bitCapInt> pows;
+    bitCapInt cMask = 0;
+    for (bitLenInt q : qubits) pows.push_back(pow2(q));
+    for (bitLenInt c : controls) {
+        pows.push_back(pow2(c));
+        cMask |= pow2(c);
+    }
+    std::sort(pows.begin(), pows.end());
+    const bitCapInt cVal = anti ? 0 : cMask;
+    std::vector<cplx<R>> v(D);
+    for (bitCapInt o = first; o < last; ++o) {
+        bitCapInt i = o;
+        for (bitCapInt p : pows) i = ((i & ~(p - 1u)) << 1u) | (i & (p - 1u));
+        i |= cVal;
+        for (size_t a = 0; a < D; ++a) v[a] = sv[i | off[a]];
+        for (size_t r = 0; r < D; ++r) {
+            const cplx<R>* row = mtrx + r * D;
+            cplx<R> acc = row[0] * v[0];
+            for (size_t c = 1; c < D; ++c) acc = acc + row[c] * v[c];
+            sv[i | off[r]] = acc;
+        }
+    }
+}
+
 template <typename R> class QInterface;
 template <typename R> using QInterfacePtr = std::shared_ptr<QInterface<R>>;
 
@@ -229,6 +292,15 @@ public:
             throw QrackError("Mtrx2qBatch: need a 4x4 per pair");
         for (size_t i = 0; i < q1s.size(); ++i) Mtrx2q(&ms[16u * i], q1s[i], q2s[i]);
     }
+
+    // dense k-qubit gate, 1 <= k <= QA_MTRXN_MAX: mtrx is row-major 2^k x 2^k,
+    // bit g of a row or column index is the value of qubits[g] (the caller's
+    // order). Controls (all set; all clear when anti) select the subspace;
+    // amplitudes outside it are left bit-identical. The matrix is applied as
+    // given: no unitarity check, no normalisation. Engines apply it in ONE
+    // pass; the default lowering copies the state to the host.
+    virtual void MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+        const std::vector<bitLenInt>& controls = {}, bool anti = false);
 
     // batched disjoint fsim layer: engines fuse in-LDS-tile pairs into one
     // pass; default lowering applies them one by one

@@ -83,6 +83,13 @@ public:
         Noise1(t);
         for (bitLenInt q : c) Noise1(q);
     }
+    void MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* m,
+        const std::vector<bitLenInt>& c = {}, bool anti = false) override
+    {
+        inner->MtrxN(qubits, m, c, anti);
+        for (bitLenInt q : qubits) Noise1(q);
+        for (bitLenInt q : c) Noise1(q);
+    }
     void Swap(bitLenInt a, bitLenInt b) override
     {
         inner->Swap(a, b);

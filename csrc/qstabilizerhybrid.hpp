@@ -172,6 +172,13 @@ public:
         SwitchToEngine();
         engine->Mtrx2q(m16, q1, q2);
     }
+    void MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+        const std::vector<bitLenInt>& controls = {}, bool anti = false) override
+    {
+        validateMtrxN(qubits, controls, this->qubitCount);
+        SwitchToEngine();
+        engine->MtrxN(qubits, mtrx, controls, anti);
+    }
     void Swap(bitLenInt q1, bitLenInt q2) override;
     void ISwap(bitLenInt q1, bitLenInt q2) override;
     void IISwap(bitLenInt q1, bitLenInt q2) override;

@@ -582,6 +582,20 @@ public:
         MaybeSeparate(q1);
         MaybeSeparate(q2);
     }
+    void MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+        const std::vector<bitLenInt>& controls = {}, bool anti = false) override
+    {
+        validateMtrxN(qubits, controls, this->qubitCount);
+        std::vector<bitLenInt> all(qubits);
+        all.insert(all.end(), controls.begin(), controls.end());
+        for (bitLenInt q : all) FlushPhasePairs(q);
+        QInterfacePtr<R> unit = EntangleAll(all);
+        std::vector<bitLenInt> mq, mc;
+        for (bitLenInt q : qubits) mq.push_back(shards[q].mapped);
+        for (bitLenInt c : controls) mc.push_back(shards[c].mapped);
+        unit->MtrxN(mq, mtrx, mc, anti);
+        for (bitLenInt q : all) MaybeSeparate(q);
+    }
     // group the batch by unit and forward fused sub-batches: a layer of 1q
     // gates on a merged unit costs ceil(k/4) passes instead of k
     void Mtrx1qBatch(

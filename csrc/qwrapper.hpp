@@ -98,6 +98,11 @@ public:
     {
         inner->Mtrx2q(m16, a, b);
     }
+    void MtrxN(const std::vector<bitLenInt>& qubits, const cplx<R>* mtrx,
+        const std::vector<bitLenInt>& controls = {}, bool anti = false) override
+    {
+        inner->MtrxN(qubits, mtrx, controls, anti);
+    }
     void CSwap(const std::vector<bitLenInt>& c, bitLenInt a, bitLenInt b) override
     {
         inner->CSwap(c, a, b);

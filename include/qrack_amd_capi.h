@@ -94,6 +94,12 @@ double qrack_expectation_pauli_sum(quid sid, uint64_t nTerms, const double* coef
  * 2 * 4^n doubles, row-major (re, im) pairs; bit j of a row or column index
  * is the value of qs[j] */
 void qrack_reduced_density_matrix(quid sid, const uint64_t* qs, uint64_t n, double* rho);
+/* dense k-qubit gate, 1 <= k <= 6: m holds 2 * 4^k doubles, a row-major
+ * 2^k x 2^k matrix of (re, im) pairs; bit g of a row or column index is the
+ * value of qs[g]. The nc controls select the subspace where all are set (all
+ * clear when anti != 0). Applied as given: no unitarity check */
+void qrack_mtrx_n(quid sid, uint64_t k, const uint64_t* qs, const double* m, uint64_t nc,
+    const uint64_t* controls, int anti);
 /* exp(-i theta P), global phase included, P the product of the listed Paulis
  * (so a lone Z is RZ(2 theta)); an all-identity string is the phase e^{-i theta} */
 void qrack_pauli_rotation(quid sid, const int* paulis, const uint64_t* qs, uint64_t n, double theta);

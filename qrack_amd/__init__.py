@@ -26,6 +26,8 @@ from qrack_amd._qrack import (  # noqa: F401
     qft_pass_plan,
     pauli_evolve_plan,
     rdm_pass_plan,
+    mtrx_n_plan,
+    MTRXN_MAX,
     RDM_MAX_QUBITS,
     RDM_REG_MAX,
     RDM_TILE_MAX,
