@@ -47,6 +47,17 @@ asan:
 	    tools/asan_smoke.cpp -o build/asan_smoke -lpthread
 	./build/asan_smoke
 
+# the adjoint-gradient calls (braket, H|psi>, gradient) on the CPU engine and
+# through the generic lowering, stand-alone under ASAN+UBSAN
+asan-adjoint:
+	@mkdir -p build
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
+	    -Icsrc csrc/qinterface.cpp csrc/qengine_cpu.cpp csrc/qengine_sparse.cpp \
+	    csrc/qstabilizer.cpp csrc/qstabilizerhybrid.cpp csrc/qunit.cpp csrc/qbdt.cpp \
+	    csrc/qpager.cpp csrc/qfactory.cpp csrc/qengine_turboquant.cpp csrc/common/parallel_for.cpp \
+	    tools/adjoint_asan.cpp -o build/adjoint_asan -lpthread
+	./build/adjoint_asan
+
 # full-suite ASAN lane: CPU-only extension instrumented with ASan+UBSan,
 # whole pytest CPU battery runs against it (catches heap bugs in every
 # layer incl. the C ABI / pinvoke compat surfaces)

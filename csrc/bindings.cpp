@@ -52,6 +52,83 @@ static std::vector<PauliTerm> pauliTermsFromTuples(
     return ts;
 }
 
+// Argument check and conversion of a dense k-qubit gate (mtrx_n, and the
+// "gate" ops of adjoint_gradient); `what` names the caller
+template <typename R>
+static void mtrxNFromPython(bitLenInt nQubits, const std::vector<long>& qubits,
+    const py::array_t<std::complex<R>, py::array::c_style | py::array::forcecast>& matrix,
+    const std::vector<long>& controls, const char* what, std::vector<bitLenInt>& qs,
+    std::vector<bitLenInt>& cs, std::vector<cplx<R>>& mm)
+{
+    const std::string w(what);
+    if (qubits.empty() || qubits.size() > (size_t)QA_MTRXN_MAX) {
+        throw QrackError(w + ": need 1 to 6 target qubits");
+    }
+    for (long b : qubits) {
+        if (b < 0 || b >= (long)nQubits) throw QrackError(w + ": qubit out of range");
+        qs.push_back((bitLenInt)b);
+    }
+    for (long b : controls) {
+        if (b < 0 || b >= (long)nQubits) throw QrackError(w + ": control out of range");
+        cs.push_back((bitLenInt)b);
+    }
+    const py::ssize_t D = (py::ssize_t)1 << qs.size();
+    const bool flat = matrix.ndim() == 1 && matrix.shape(0) == D * D;
+    const bool square = matrix.ndim() == 2 && matrix.shape(0) == D && matrix.shape(1) == D;
+    if (!flat && !square) throw QrackError(w + ": need a 2^k x 2^k matrix, 4^k entries");
+    mm.resize((size_t)(D * D));
+    for (py::ssize_t i = 0; i < D * D; ++i) mm[(size_t)i] = from_std<R>(matrix.data()[i]);
+}
+
+// ("rot", qubits, paulis, theta[, trainable]) and
+// ("gate", qubits, matrix[, controls, anti]) tuples -> AdjointOp list
+template <typename R>
+static std::vector<AdjointOp<R>> adjointOpsFromTuples(bitLenInt nQubits, const py::list& ops)
+{
+    using Mat = py::array_t<std::complex<R>, py::array::c_style | py::array::forcecast>;
+    std::vector<AdjointOp<R>> out;
+    for (const py::handle& h : ops) {
+        if (!py::isinstance<py::tuple>(h)) throw QrackError("adjoint_gradient: an op must be a tuple");
+        const py::tuple t = py::reinterpret_borrow<py::tuple>(h);
+        if (t.size() < 1 || !py::isinstance<py::str>(t[0]))
+            throw QrackError("adjoint_gradient: an op starts with its tag, \"rot\" or \"gate\"");
+        const std::string tag = t[0].cast<std::string>();
+        AdjointOp<R> op;
+        if (tag == "rot") {
+            if (t.size() != 4 && t.size() != 5)
+                throw QrackError("adjoint_gradient: a rot op is (\"rot\", qubits, paulis, theta[, trainable])");
+            op.kind = AdjointOp<R>::Rotation;
+            for (long b : t[1].cast<std::vector<long>>()) {
+                if (b < 0 || b >= (long)nQubits) throw QrackError("adjoint_gradient: qubit out of range");
+                op.qubits.push_back((bitLenInt)b);
+            }
+            for (int p : t[2].cast<std::vector<int>>()) {
+                if (p < 0 || p > 3) throw QrackError("adjoint_gradient: bad Pauli code");
+                op.paulis.push_back((Pauli)p);
+            }
+            op.theta = t[3].cast<double>();
+            op.trainable = t.size() == 5 ? t[4].cast<bool>() : true;
+        } else if (tag == "gate") {
+            if (t.size() != 3 && t.size() != 5)
+                throw QrackError("adjoint_gradient: a gate op is (\"gate\", qubits, matrix[, controls, anti])");
+            op.kind = AdjointOp<R>::Gate;
+            const std::vector<long> controls = t.size() == 5 ? t[3].cast<std::vector<long>>() : std::vector<long>();
+            op.anti = t.size() == 5 ? t[4].cast<bool>() : false;
+            const Mat matrix = Mat::ensure(t[2]);
+            if (!matrix) {
+                PyErr_Clear();
+                throw QrackError("adjoint_gradient: a gate's matrix must be a complex array");
+            }
+            mtrxNFromPython<R>(nQubits, t[1].cast<std::vector<long>>(), matrix, controls,
+                "adjoint_gradient", op.qubits, op.controls, op.mtrx);
+        } else {
+            throw QrackError("adjoint_gradient: bad op tag \"" + tag + "\"");
+        }
+        out.push_back(std::move(op));
+    }
+    return out;
+}
+
 template <typename R> static void bindQInterface(py::module_& m, const char* name)
 {
     using QI = QInterface<R>;
@@ -106,24 +183,9 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
             [](QI& q, std::vector<long> qubits,
                 py::array_t<C, py::array::c_style | py::array::forcecast> matrix,
                 std::vector<long> controls, bool anti) {
-                if (qubits.empty() || qubits.size() > (size_t)QA_MTRXN_MAX) {
-                    throw QrackError("mtrx_n: need 1 to 6 target qubits");
-                }
                 std::vector<bitLenInt> qs, cs;
-                for (long b : qubits) {
-                    if (b < 0 || b >= (long)q.GetQubitCount()) throw QrackError("mtrx_n: qubit out of range");
-                    qs.push_back((bitLenInt)b);
-                }
-                for (long b : controls) {
-                    if (b < 0 || b >= (long)q.GetQubitCount()) throw QrackError("mtrx_n: control out of range");
-                    cs.push_back((bitLenInt)b);
-                }
-                const py::ssize_t D = (py::ssize_t)1 << qs.size();
-                const bool flat = matrix.ndim() == 1 && matrix.shape(0) == D * D;
-                const bool square = matrix.ndim() == 2 && matrix.shape(0) == D && matrix.shape(1) == D;
-                if (!flat && !square) throw QrackError("mtrx_n: need a 2^k x 2^k matrix, 4^k entries");
-                std::vector<cplx<R>> mm((size_t)(D * D));
-                for (py::ssize_t i = 0; i < D * D; ++i) mm[(size_t)i] = from_std<R>(matrix.data()[i]);
+                std::vector<cplx<R>> mm;
+                mtrxNFromPython<R>(q.GetQubitCount(), qubits, matrix, controls, "mtrx_n", qs, cs, mm);
                 q.MtrxN(qs, mm.data(), cs, anti);
             },
             py::arg("qubits"), py::arg("matrix"), py::arg("controls") = std::vector<long>(),
@@ -501,6 +563,42 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
             py::arg("terms"), py::arg("time"), py::arg("steps") = 1, py::arg("order") = 1,
             "exp(-i time H) for H = sum of (coeff, [qubits], [paulis]) terms as a first- or "
             "second-order product formula of `steps` steps")
+        .def("pauli_sum_braket",
+            [](QI& q, Ptr bra,
+                std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms) {
+                if (!bra) throw QrackError("pauli_sum_braket: bra is None");
+                const cplx<double> b = q.PauliSumBraket(bra, pauliTermsFromTuples(terms, "pauli_sum_braket"));
+                return std::complex<double>(b.re, b.im);
+            },
+            py::arg("bra"), py::arg("terms"),
+            "<bra|H|self> for H = sum of (coeff, [qubits], [paulis]) terms: linear in self, "
+            "conjugate-linear in bra; neither is modified and neither needs unit norm")
+        .def("pauli_sum_apply_into",
+            [](QI& q, std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms,
+                Ptr dest) {
+                if (!dest) throw QrackError("pauli_sum_apply_into: dest is None");
+                q.PauliSumApplyInto(pauliTermsFromTuples(terms, "pauli_sum_apply_into"), dest);
+            },
+            py::arg("terms"), py::arg("dest"),
+            "overwrite dest (same width, stack and precision, not self) with the unnormalised "
+            "vector H|self>; self is untouched")
+        .def("adjoint_gradient",
+            [](QI& q, py::list ops,
+                std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms) {
+                const std::vector<AdjointOp<R>> aops = adjointOpsFromTuples<R>(q.GetQubitCount(), ops);
+                std::vector<double> grad;
+                const double e
+                    = q.AdjointGradient(aops, pauliTermsFromTuples(terms, "adjoint_gradient"), grad);
+                py::array_t<double> g((py::ssize_t)grad.size());
+                std::copy(grad.begin(), grad.end(), g.mutable_data());
+                return py::make_tuple(e, g);
+            },
+            py::arg("ops"), py::arg("terms"),
+            "run ops on the current state and return (E, dE/dtheta) for E = <H> by the adjoint "
+            "method. ops are (\"rot\", qubits, paulis, theta[, trainable]) for exp(-i theta P) and "
+            "(\"gate\", qubits, matrix[, controls, anti]) for a fixed unitary (mtrx_n arguments; not "
+            "checked for unitarity). The gradient has one entry per trainable rotation, in op "
+            "order. On return the simulator holds its initial state again, to rounding")
         .def("prob_bits_all",
             [](QI& q, std::vector<bitLenInt> bits) {
                 py::array_t<double> out((py::ssize_t)pow2((bitLenInt)bits.size()));

@@ -79,6 +79,52 @@ template <typename F> double guardedD(quid sid, F&& fn, double dflt = 0.0)
     }
 }
 
+// flat term arrays -> PauliTerm list; `what` names the caller
+std::vector<PauliTerm> flatPauliTerms(uint64_t nTerms, const double* coeffs, const uint64_t* termLens,
+    const uint64_t* qs, const int* paulis, const char* what)
+{
+    std::vector<PauliTerm> terms(nTerms);
+    uint64_t at = 0;
+    for (uint64_t t = 0; t < nTerms; ++t) {
+        terms[t].coeff = coeffs[t];
+        for (uint64_t i = 0; i < termLens[t]; ++i, ++at) {
+            if (paulis[at] < 0 || paulis[at] > 3) throw QrackError(std::string(what) + ": bad Pauli code");
+            terms[t].bits.push_back((bitLenInt)qs[at]);
+            terms[t].paulis.push_back((Pauli)paulis[at]);
+        }
+    }
+    return terms;
+}
+
+// run fn(a, b) with both slots locked (one lock when the handles are equal);
+// an error lands on the first slot
+template <typename F> void guarded2(quid sid, quid other, F&& fn)
+{
+    SimSlotPtr a = slot(sid);
+    SimSlotPtr b = slot(other);
+    if (!a) return;
+    if (!b) {
+        a->error = 1;
+        return;
+    }
+    std::unique_lock<std::mutex> la(a->op, std::defer_lock);
+    std::unique_lock<std::mutex> lb;
+    if (a.get() == b.get()) {
+        la.lock();
+    } else {
+        lb = std::unique_lock<std::mutex>(b->op, std::defer_lock);
+        std::lock(la, lb);
+    }
+    try {
+        fn(*a, *b);
+    } catch (const std::bad_alloc&) {
+        a->error = 2;
+    } catch (const std::exception& e) {
+        if (std::getenv("QRACK_CAPI_DEBUG")) fprintf(stderr, "capi error: %s\n", e.what());
+        a->error = 1;
+    }
+}
+
 // apply op to whichever precision is active
 #define FOR_SIM(s, expr)                                                                           \
     do {                                                                                           \
@@ -539,17 +585,8 @@ double qrack_expectation_pauli_sum(quid sid, uint64_t nTerms, const double* coef
     const uint64_t* termLens, const uint64_t* qs, const int* paulis)
 {
     return guardedD(sid, [&](SimSlot& s) -> double {
-        std::vector<PauliTerm> terms(nTerms);
-        uint64_t at = 0;
-        for (uint64_t t = 0; t < nTerms; ++t) {
-            terms[t].coeff = coeffs[t];
-            for (uint64_t i = 0; i < termLens[t]; ++i, ++at) {
-                if (paulis[at] < 0 || paulis[at] > 3)
-                    throw QrackError("qrack_expectation_pauli_sum: bad Pauli code");
-                terms[t].bits.push_back((bitLenInt)qs[at]);
-                terms[t].paulis.push_back((Pauli)paulis[at]);
-            }
-        }
+        const std::vector<PauliTerm> terms
+            = flatPauliTerms(nTerms, coeffs, termLens, qs, paulis, "qrack_expectation_pauli_sum");
         double e = 0;
         FOR_SIM(s, e = q.ExpectationPauliSum(terms));
         return e;
@@ -616,18 +653,46 @@ void qrack_evolve_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
     int order)
 {
     guarded(sid, [&](SimSlot& s) {
-        std::vector<PauliTerm> terms(nTerms);
-        uint64_t at = 0;
-        for (uint64_t t = 0; t < nTerms; ++t) {
-            terms[t].coeff = coeffs[t];
-            for (uint64_t i = 0; i < termLens[t]; ++i, ++at) {
-                if (paulis[at] < 0 || paulis[at] > 3)
-                    throw QrackError("qrack_evolve_pauli_sum: bad Pauli code");
-                terms[t].bits.push_back((bitLenInt)qs[at]);
-                terms[t].paulis.push_back((Pauli)paulis[at]);
-            }
-        }
+        const std::vector<PauliTerm> terms
+            = flatPauliTerms(nTerms, coeffs, termLens, qs, paulis, "qrack_evolve_pauli_sum");
         FOR_SIM(s, q.EvolvePauliSum(terms, time, steps, order));
+    });
+}
+
+void qrack_pauli_sum_braket(quid sid, quid bra, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, double* re, double* im)
+{
+    *re = 0;
+    *im = 0;
+    guarded2(sid, bra, [&](SimSlot& s, SimSlot& b) {
+        const std::vector<PauliTerm> terms
+            = flatPauliTerms(nTerms, coeffs, termLens, qs, paulis, "qrack_pauli_sum_braket");
+        cplx<double> v(0, 0);
+        if (s.f && b.f) {
+            v = s.f->PauliSumBraket(b.f, terms);
+        } else if (s.d && b.d) {
+            v = s.d->PauliSumBraket(b.d, terms);
+        } else {
+            throw QrackError("qrack_pauli_sum_braket: the two simulators differ in precision");
+        }
+        *re = v.re;
+        *im = v.im;
+    });
+}
+
+void qrack_pauli_sum_apply_into(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, quid dest)
+{
+    guarded2(sid, dest, [&](SimSlot& s, SimSlot& d) {
+        const std::vector<PauliTerm> terms
+            = flatPauliTerms(nTerms, coeffs, termLens, qs, paulis, "qrack_pauli_sum_apply_into");
+        if (s.f && d.f) {
+            s.f->PauliSumApplyInto(terms, d.f);
+        } else if (s.d && d.d) {
+            s.d->PauliSumApplyInto(terms, d.d);
+        } else {
+            throw QrackError("qrack_pauli_sum_apply_into: the two simulators differ in precision");
+        }
     });
 }
 

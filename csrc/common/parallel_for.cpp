@@ -168,4 +168,29 @@ double ParallelFor::par_sum(bitCapInt maxI, const std::function<double(const bit
     return total;
 }
 
+void ParallelFor::par_sum2(bitCapInt maxI,
+    const std::function<void(const bitCapInt&, double&, double&)>& fn, double& re, double& im) const
+{
+    re = 0;
+    im = 0;
+    if (maxI < (pStride_ << 1u)) {
+        for (bitCapInt i = 0; i < maxI; ++i) fn(i, re, im);
+        return;
+    }
+    const unsigned nw = (unsigned)std::min<bitCapInt>(numCores(), (maxI + pStride_ - 1) / pStride_);
+    const bitCapInt slice = (maxI + nw - 1) / nw;
+    std::vector<double> partials(2u * nw, 0.0);
+    ThreadPool::instance().run(nw, [&](unsigned w) {
+        double r = 0, m = 0;
+        const bitCapInt lo = std::min(maxI, w * slice), hi = std::min(maxI, lo + slice);
+        for (bitCapInt i = lo; i < hi; ++i) fn(i, r, m);
+        partials[2u * w] = r;
+        partials[2u * w + 1u] = m;
+    });
+    for (unsigned w = 0; w < nw; ++w) {
+        re += partials[2u * w];
+        im += partials[2u * w + 1u];
+    }
+}
+
 } // namespace qrack_amd

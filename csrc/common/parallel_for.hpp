@@ -64,6 +64,13 @@ public:
     // parallel sum reduction of fn over [0, maxI)
     double par_sum(bitCapInt maxI, const std::function<double(const bitCapInt&)>& fn) const;
 
+    // parallel complex sum over [0, maxI): fn adds item i's share to the two
+    // sums it is handed (and may write memory that only item i owns). Every
+    // worker owns one contiguous slice and a private pair of double sums,
+    // added in worker order at the end, so a repeat gives the same bits.
+    void par_sum2(bitCapInt maxI, const std::function<void(const bitCapInt&, double&, double&)>& fn,
+        double& re, double& im) const;
+
     bitCapInt parStride() const { return pStride_; }
     unsigned numCores() const { return ThreadPool::instance().numCores(); }
 

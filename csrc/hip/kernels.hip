@@ -3776,6 +3776,545 @@ void launchPauliEvolve(cplx<R>* sv, const PauliEvolveArgs& a, hipStream_t stream
     }
 }
 
+// ---- Pauli brakets, H|psi>, fused adjoint step ------------------------------------
+//
+// All three walk the pairs (i, j = i^x) of k_pauli_group / k_pauli_evolve, in
+// the same three addressing modes, so every amplitude of every vector involved
+// is loaded once (and, where written, stored once by exactly one thread).
+// With W(i) = wr(i) + i wi(i) the summed weight of a group at index i, the
+// partner's weight is conj(W(i)): a term of the re set has an even number of
+// Y factors, popcount(x & z) is even and its sign is the same at i and i^x;
+// a term of the im set has an odd number and its sign flips. No second
+// popcount over the index is needed.
+
+// reduction grid of the pair kernels: one partial per block, and the
+// QRACK_GPU_BLOCKS cap so that a small state can drive the stride loop
+static inline int gridForPairs(bitCapInt nItems)
+{
+    int grid = gridForReduce(nItems);
+    const int cap = maxBlocks();
+    if (cap > 0 && grid > cap) grid = cap;
+    return grid;
+}
+
+// block sums of a complex value in a fixed order; the two parts have an LDS
+// array each (two calls of blockSumStore would race on its one array)
+__device__ __forceinline__ void blockSumStore2(double re, double im, double* dstRe, double* dstIm)
+{
+    re = waveReduceSum(re);
+    im = waveReduceSum(im);
+    __shared__ double waveRe[QA_BLOCK / 64];
+    __shared__ double waveIm[QA_BLOCK / 64];
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    if (lane == 0) {
+        waveRe[wid] = re;
+        waveIm[wid] = im;
+    }
+    __syncthreads();
+    if (wid == 0) {
+        double tr = (lane < QA_BLOCK / 64) ? waveRe[lane] : 0.0;
+        double ti = (lane < QA_BLOCK / 64) ? waveIm[lane] : 0.0;
+        tr = waveReduceSum(tr);
+        ti = waveReduceSum(ti);
+        if (lane == 0) {
+            *dstRe = tr;
+            *dstIm = ti;
+        }
+    }
+}
+
+// pair (i, j): W conj(q) a + conj(W) conj(p) b, with a = psi[i], b = psi[j],
+// p = bra[i], q = bra[j] and W = wr + i wi; products in R, sums in double
+template <typename R>
+__device__ __forceinline__ void pauliBraketPair(R ar, R ai, R br, R bi, R pr, R pi, R qr, R qi,
+    double wr, double wi, double& re, double& im)
+{
+    const R t1r = qr * ar + qi * ai, t1i = qr * ai - qi * ar;
+    const R t2r = pr * br + pi * bi, t2i = pr * bi - pi * br;
+    re += wr * ((double)t1r + (double)t2r) - wi * ((double)t1i - (double)t2i);
+    im += wr * ((double)t1i + (double)t2i) + wi * ((double)t1r - (double)t2r);
+}
+
+// w conj(p) a: a diagonal term, and the identity's share of any pair
+template <typename R>
+__device__ __forceinline__ void pauliBraketDiag(R ar, R ai, R pr, R pi, double w, double& re, double& im)
+{
+    re += w * (double)(pr * ar + pi * ai);
+    im += w * (double)(pr * ai - pi * ar);
+}
+
+// <bra| sum_t c_t P_t |psi> for one group with x != 0, plus ident <bra|psi>
+template <typename R, int MODE>
+__global__ void k_pauli_braket(const cplx<R>* psi, const cplx<R>* bra, PauliArgs a, double ident,
+    bitCapInt nItems, bitCapInt topPow, double* partialsRe, double* partialsIm)
+{
+    double re = 0, im = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        double wr0, wr1, wi0, wi1;
+        if constexpr (MODE == 0) {
+            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
+            const double2 A = reinterpret_cast<const double2*>(psi)[i];
+            const double2 B = reinterpret_cast<const double2*>(psi)[i ^ a.x];
+            const double2 P = reinterpret_cast<const double2*>(bra)[i];
+            const double2 Q = reinterpret_cast<const double2*>(bra)[i ^ a.x];
+            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            pauliBraketPair<double>(A.x, A.y, B.x, B.y, P.x, P.y, Q.x, Q.y, wr0, wi0, re, im);
+            if (ident != 0) {
+                pauliBraketDiag<double>(A.x, A.y, P.x, P.y, ident, re, im);
+                pauliBraketDiag<double>(B.x, B.y, Q.x, Q.y, ident, re, im);
+            }
+        } else if constexpr (MODE == 1) {
+            const bitCapInt j = v << 1u;
+            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
+            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
+            const float4 A = reinterpret_cast<const float4*>(psi)[ia];
+            float4 B = reinterpret_cast<const float4*>(psi)[ib];
+            const float4 P = reinterpret_cast<const float4*>(bra)[ia];
+            float4 Q = reinterpret_cast<const float4*>(bra)[ib];
+            if (a.x & 1u) {
+                B = make_float4(B.z, B.w, B.x, B.y);
+                Q = make_float4(Q.z, Q.w, Q.x, Q.y);
+            }
+            pauliWeights<true>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<true>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            pauliBraketPair<float>(A.x, A.y, B.x, B.y, P.x, P.y, Q.x, Q.y, wr0, wi0, re, im);
+            pauliBraketPair<float>(A.z, A.w, B.z, B.w, P.z, P.w, Q.z, Q.w, wr1, wi1, re, im);
+            if (ident != 0) {
+                pauliBraketDiag<float>(A.x, A.y, P.x, P.y, ident, re, im);
+                pauliBraketDiag<float>(A.z, A.w, P.z, P.w, ident, re, im);
+                pauliBraketDiag<float>(B.x, B.y, Q.x, Q.y, ident, re, im);
+                pauliBraketDiag<float>(B.z, B.w, Q.z, Q.w, ident, re, im);
+            }
+        } else {
+            const bitCapInt i = v << 1u;
+            const float4 A = reinterpret_cast<const float4*>(psi)[v];
+            const float4 P = reinterpret_cast<const float4*>(bra)[v];
+            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            pauliBraketPair<float>(A.x, A.y, A.z, A.w, P.x, P.y, P.z, P.w, wr0, wi0, re, im);
+            if (ident != 0) {
+                pauliBraketDiag<float>(A.x, A.y, P.x, P.y, ident, re, im);
+                pauliBraketDiag<float>(A.z, A.w, P.z, P.w, ident, re, im);
+            }
+        }
+    }
+    blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
+}
+
+// x == 0: sum_i (ident + sum_t c_t (-1)^popcount(i&z_t)) conj(bra[i]) psi[i]
+template <typename R>
+__global__ void k_pauli_braket_diag(const cplx<R>* psi, const cplx<R>* bra, PauliArgs a, double ident,
+    bitCapInt nItems, double* partialsRe, double* partialsIm)
+{
+    double re = 0, im = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        double w0, w1;
+        if constexpr (sizeof(R) == 4) {
+            const float4 A = reinterpret_cast<const float4*>(psi)[v];
+            const float4 P = reinterpret_cast<const float4*>(bra)[v];
+            pauliWeights<true>(a, 0, a.nTerms, v << 1u, w0, w1);
+            pauliBraketDiag<float>(A.x, A.y, P.x, P.y, w0 + ident, re, im);
+            pauliBraketDiag<float>(A.z, A.w, P.z, P.w, w1 + ident, re, im);
+        } else {
+            const double2 A = reinterpret_cast<const double2*>(psi)[v];
+            const double2 P = reinterpret_cast<const double2*>(bra)[v];
+            pauliWeights<false>(a, 0, a.nTerms, v, w0, w1);
+            pauliBraketDiag<double>(A.x, A.y, P.x, P.y, w0 + ident, re, im);
+        }
+    }
+    blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
+}
+
+// stage 2: fold one launch's block partials, in a fixed order, into (re, im)
+__global__ void k_pauli_finish2(const double* partialsRe, const double* partialsIm, int n, double* result)
+{
+    double re = 0, im = 0;
+    for (int k = threadIdx.x; k < n; k += QA_BLOCK) {
+        re += partialsRe[k];
+        im += partialsIm[k];
+    }
+    blockSumStore2(re, im, result, result + 1);
+}
+
+// items and top power of the pair walk: an item is one 16-byte access per
+// stream. mode -1 is the diagonal kernel.
+template <typename R> static int pauliPairMode(bitCapInt x, bitCapInt nAmps, bitCapInt& nItems, bitCapInt& topPow)
+{
+    if (!x) {
+        nItems = (sizeof(R) == 4) ? (nAmps >> 1u) : nAmps;
+        topPow = 0;
+        return -1;
+    }
+    topPow = ONE_BCI << (63 - __builtin_clzll(x));
+    if (sizeof(R) == 8) {
+        nItems = nAmps >> 1u;
+        return 0;
+    }
+    if (x == 1u) {
+        nItems = nAmps >> 1u;
+        return 2;
+    }
+    nItems = nAmps >> 2u;
+    return 1;
+}
+
+template <typename R>
+void launchPauliBraket(const cplx<R>* psi, const cplx<R>* bra, const PauliArgs& a, double ident,
+    double* partialsDev, double* resultDev, hipStream_t stream)
+{
+    bitCapInt nItems, topPow;
+    const int mode = pauliPairMode<R>(a.x, a.nAmps, nItems, topPow);
+    const int grid = gridForPairs(nItems);
+    double* pRe = partialsDev;
+    double* pIm = partialsDev + QA_REDUCE_MAX_BLOCKS;
+    const dim3 g(grid), b(QA_BLOCK);
+    if (mode < 0) {
+        hipLaunchKernelGGL((k_pauli_braket_diag<R>), g, b, 0, stream, psi, bra, a, ident, nItems, pRe, pIm);
+    } else if constexpr (sizeof(R) == 4) {
+        if (mode == 2) {
+            hipLaunchKernelGGL(
+                (k_pauli_braket<R, 2>), g, b, 0, stream, psi, bra, a, ident, nItems, topPow, pRe, pIm);
+        } else {
+            hipLaunchKernelGGL(
+                (k_pauli_braket<R, 1>), g, b, 0, stream, psi, bra, a, ident, nItems, topPow, pRe, pIm);
+        }
+    } else {
+        hipLaunchKernelGGL(
+            (k_pauli_braket<R, 0>), g, b, 0, stream, psi, bra, a, ident, nItems, topPow, pRe, pIm);
+    }
+    hipLaunchKernelGGL(k_pauli_finish2, dim3(1), dim3(QA_BLOCK), 0, stream, pRe, pIm, grid, resultDev);
+}
+
+// (re, im) <- (re, im) + (wr + i wi) (ar + i ai), everything in R
+template <typename R>
+__device__ __forceinline__ void pauliApplyMad(R wr, R wi, R ar, R ai, R& re, R& im)
+{
+    re += wr * ar - wi * ai;
+    im += wr * ai + wi * ar;
+}
+
+// dest (+)= (sum_t c_t P_t) psi for one group with x != 0: dest[i] takes
+// W(j) psi[j] and dest[j] takes W(i) psi[i]. FIRST: dest is written without
+// being read, and ident * psi rides along (psi[i] and psi[j] are in registers).
+template <typename R, int MODE, bool FIRST>
+__global__ void k_pauli_apply(const cplx<R>* psi, cplx<R>* dest, PauliArgs a, double ident,
+    bitCapInt nItems, bitCapInt topPow)
+{
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    const R id = (R)ident;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        double wr0, wr1, wi0, wi1;
+        if constexpr (MODE == 0) {
+            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
+            const double2 A = reinterpret_cast<const double2*>(psi)[i];
+            const double2 B = reinterpret_cast<const double2*>(psi)[i ^ a.x];
+            double2* d = reinterpret_cast<double2*>(dest);
+            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            double2 DA, DB;
+            if constexpr (FIRST) {
+                DA = make_double2(id * A.x, id * A.y);
+                DB = make_double2(id * B.x, id * B.y);
+            } else {
+                DA = d[i];
+                DB = d[i ^ a.x];
+            }
+            pauliApplyMad<double>(wr0, -wi0, B.x, B.y, DA.x, DA.y);
+            pauliApplyMad<double>(wr0, wi0, A.x, A.y, DB.x, DB.y);
+            d[i] = DA;
+            d[i ^ a.x] = DB;
+        } else if constexpr (MODE == 1) {
+            const bitCapInt j = v << 1u;
+            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
+            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
+            const float4 A = reinterpret_cast<const float4*>(psi)[ia];
+            float4 B = reinterpret_cast<const float4*>(psi)[ib];
+            float4* d = reinterpret_cast<float4*>(dest);
+            const bool swapped = (a.x & 1u) != 0;
+            if (swapped) B = make_float4(B.z, B.w, B.x, B.y);
+            pauliWeights<true>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<true>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            float4 DA, DB;
+            if constexpr (FIRST) {
+                DA = make_float4(id * A.x, id * A.y, id * A.z, id * A.w);
+                DB = make_float4(id * B.x, id * B.y, id * B.z, id * B.w);
+            } else {
+                DA = d[ia];
+                DB = d[ib];
+                if (swapped) DB = make_float4(DB.z, DB.w, DB.x, DB.y);
+            }
+            pauliApplyMad<float>((float)wr0, -(float)wi0, B.x, B.y, DA.x, DA.y);
+            pauliApplyMad<float>((float)wr1, -(float)wi1, B.z, B.w, DA.z, DA.w);
+            pauliApplyMad<float>((float)wr0, (float)wi0, A.x, A.y, DB.x, DB.y);
+            pauliApplyMad<float>((float)wr1, (float)wi1, A.z, A.w, DB.z, DB.w);
+            if (swapped) DB = make_float4(DB.z, DB.w, DB.x, DB.y);
+            d[ia] = DA;
+            d[ib] = DB;
+        } else {
+            const bitCapInt i = v << 1u;
+            const float4 A = reinterpret_cast<const float4*>(psi)[v];
+            float4* d = reinterpret_cast<float4*>(dest);
+            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            float4 D;
+            if constexpr (FIRST) {
+                D = make_float4(id * A.x, id * A.y, id * A.z, id * A.w);
+            } else {
+                D = d[v];
+            }
+            pauliApplyMad<float>((float)wr0, -(float)wi0, A.z, A.w, D.x, D.y);
+            pauliApplyMad<float>((float)wr0, (float)wi0, A.x, A.y, D.z, D.w);
+            d[v] = D;
+        }
+    }
+}
+
+// x == 0: dest[i] (+)= (sum_t c_t (-1)^popcount(i&z_t)) psi[i]; FIRST as above
+template <typename R, bool FIRST>
+__global__ void k_pauli_apply_diag(const cplx<R>* psi, cplx<R>* dest, PauliArgs a, double ident, bitCapInt nItems)
+{
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        double w0, w1;
+        if constexpr (sizeof(R) == 4) {
+            const float4 A = reinterpret_cast<const float4*>(psi)[v];
+            float4* d = reinterpret_cast<float4*>(dest);
+            pauliWeights<true>(a, 0, a.nTerms, v << 1u, w0, w1);
+            if constexpr (FIRST) {
+                const float f0 = (float)(w0 + ident), f1 = (float)(w1 + ident);
+                d[v] = make_float4(f0 * A.x, f0 * A.y, f1 * A.z, f1 * A.w);
+            } else {
+                const float f0 = (float)w0, f1 = (float)w1;
+                float4 D = d[v];
+                D.x += f0 * A.x;
+                D.y += f0 * A.y;
+                D.z += f1 * A.z;
+                D.w += f1 * A.w;
+                d[v] = D;
+            }
+        } else {
+            const double2 A = reinterpret_cast<const double2*>(psi)[v];
+            double2* d = reinterpret_cast<double2*>(dest);
+            pauliWeights<false>(a, 0, a.nTerms, v, w0, w1);
+            if constexpr (FIRST) {
+                d[v] = make_double2((w0 + ident) * A.x, (w0 + ident) * A.y);
+            } else {
+                double2 D = d[v];
+                D.x += w0 * A.x;
+                D.y += w0 * A.y;
+                d[v] = D;
+            }
+        }
+    }
+}
+
+template <typename R, bool FIRST>
+static void launchPauliApplyFirst(const cplx<R>* psi, cplx<R>* dest, const PauliArgs& a, double ident,
+    hipStream_t stream)
+{
+    bitCapInt nItems, topPow;
+    const int mode = pauliPairMode<R>(a.x, a.nAmps, nItems, topPow);
+    const dim3 g(gridForPairs(nItems)), b(QA_BLOCK);
+    if (mode < 0) {
+        hipLaunchKernelGGL((k_pauli_apply_diag<R, FIRST>), g, b, 0, stream, psi, dest, a, ident, nItems);
+    } else if constexpr (sizeof(R) == 4) {
+        if (mode == 2) {
+            hipLaunchKernelGGL(
+                (k_pauli_apply<R, 2, FIRST>), g, b, 0, stream, psi, dest, a, ident, nItems, topPow);
+        } else {
+            hipLaunchKernelGGL(
+                (k_pauli_apply<R, 1, FIRST>), g, b, 0, stream, psi, dest, a, ident, nItems, topPow);
+        }
+    } else {
+        hipLaunchKernelGGL((k_pauli_apply<R, 0, FIRST>), g, b, 0, stream, psi, dest, a, ident, nItems, topPow);
+    }
+}
+
+template <typename R>
+void launchPauliApply(const cplx<R>* psi, cplx<R>* dest, const PauliArgs& a, double ident, bool first,
+    hipStream_t stream)
+{
+    if (first) {
+        launchPauliApplyFirst<R, true>(psi, dest, a, ident, stream);
+    } else {
+        launchPauliApplyFirst<R, false>(psi, dest, a, 0.0, stream);
+    }
+}
+
+// sign of the one string at index i (and at i + 1 when TWO): parity of i & z
+template <bool TWO>
+__device__ __forceinline__ void pauliAdjointParity(bitCapInt z, bitCapInt i, unsigned& p0, unsigned& p1)
+{
+    p0 = __popcll(i & z) & 1u;
+    p1 = TWO ? (p0 ^ (unsigned)(z & 1u)) : 0u;
+}
+
+// One step of the adjoint sweep for a trainable rotation exp(-i theta P): sum
+// <lam|P|psi> over the pairs, then apply exp(+i theta P) to both vectors while
+// their amplitudes are in registers. P commutes with the rotation, so the sum
+// has the same value before and after. The host supplies cos and sin of the
+// angle (the SINGLE path of k_pauli_evolve): no device transcendental.
+template <typename R, int MODE, bool NT>
+__global__ void k_pauli_adjoint(cplx<R>* psi, cplx<R>* lam, PauliAdjointArgs a, bitCapInt nItems,
+    bitCapInt topPow, double* partialsRe, double* partialsIm)
+{
+    double re = 0, im = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    const bool isIm = a.im != 0;
+    const R c = (R)a.cs, s = (R)a.sn;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        unsigned p0, p1;
+        if constexpr (MODE == 0) {
+            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
+            double2* ps = reinterpret_cast<double2*>(psi);
+            double2* pl = reinterpret_cast<double2*>(lam);
+            double2 A = ps[i], B = ps[i ^ a.x], P = pl[i], Q = pl[i ^ a.x];
+            pauliAdjointParity<false>(a.z, i, p0, p1);
+            const double w = p0 ? -a.w : a.w;
+            pauliBraketPair<double>(
+                A.x, A.y, B.x, B.y, P.x, P.y, Q.x, Q.y, isIm ? 0.0 : w, isIm ? w : 0.0, re, im);
+            const double s0 = p0 ? -s : s;
+            pauliEvolveRot<double>(isIm, c, s0, A.x, A.y, B.x, B.y);
+            pauliEvolveRot<double>(isIm, c, s0, P.x, P.y, Q.x, Q.y);
+            ps[i] = A;
+            ps[i ^ a.x] = B;
+            pl[i] = P;
+            pl[i ^ a.x] = Q;
+        } else if constexpr (MODE == 1) {
+            const bitCapInt j = v << 1u;
+            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
+            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
+            float4* ps = reinterpret_cast<float4*>(psi);
+            float4* pl = reinterpret_cast<float4*>(lam);
+            float4 A = ld4<NT>(ps + ia), B = ld4<NT>(ps + ib);
+            float4 P = ld4<NT>(pl + ia), Q = ld4<NT>(pl + ib);
+            const bool swapped = (a.x & 1u) != 0;
+            if (swapped) {
+                B = make_float4(B.z, B.w, B.x, B.y);
+                Q = make_float4(Q.z, Q.w, Q.x, Q.y);
+            }
+            pauliAdjointParity<true>(a.z, i, p0, p1);
+            const double w0 = p0 ? -a.w : a.w, w1 = p1 ? -a.w : a.w;
+            pauliBraketPair<float>(
+                A.x, A.y, B.x, B.y, P.x, P.y, Q.x, Q.y, isIm ? 0.0 : w0, isIm ? w0 : 0.0, re, im);
+            pauliBraketPair<float>(
+                A.z, A.w, B.z, B.w, P.z, P.w, Q.z, Q.w, isIm ? 0.0 : w1, isIm ? w1 : 0.0, re, im);
+            const float s0 = p0 ? -s : s, s1 = p1 ? -s : s;
+            pauliEvolveRot<float>(isIm, c, s0, A.x, A.y, B.x, B.y);
+            pauliEvolveRot<float>(isIm, c, s1, A.z, A.w, B.z, B.w);
+            pauliEvolveRot<float>(isIm, c, s0, P.x, P.y, Q.x, Q.y);
+            pauliEvolveRot<float>(isIm, c, s1, P.z, P.w, Q.z, Q.w);
+            if (swapped) {
+                B = make_float4(B.z, B.w, B.x, B.y);
+                Q = make_float4(Q.z, Q.w, Q.x, Q.y);
+            }
+            st4<NT>(ps + ia, A);
+            st4<NT>(ps + ib, B);
+            st4<NT>(pl + ia, P);
+            st4<NT>(pl + ib, Q);
+        } else {
+            const bitCapInt i = v << 1u;
+            float4* ps = reinterpret_cast<float4*>(psi);
+            float4* pl = reinterpret_cast<float4*>(lam);
+            float4 A = ld4<NT>(ps + v), P = ld4<NT>(pl + v);
+            pauliAdjointParity<false>(a.z, i, p0, p1);
+            const double w = p0 ? -a.w : a.w;
+            pauliBraketPair<float>(
+                A.x, A.y, A.z, A.w, P.x, P.y, P.z, P.w, isIm ? 0.0 : w, isIm ? w : 0.0, re, im);
+            const float s0 = p0 ? -s : s;
+            pauliEvolveRot<float>(isIm, c, s0, A.x, A.y, A.z, A.w);
+            pauliEvolveRot<float>(isIm, c, s0, P.x, P.y, P.z, P.w);
+            st4<NT>(ps + v, A);
+            st4<NT>(pl + v, P);
+        }
+    }
+    blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
+}
+
+// x == 0: the string is diagonal; both vectors are multiplied by e^{-i angle(i)}
+template <typename R, bool NT>
+__global__ void k_pauli_adjoint_diag(cplx<R>* psi, cplx<R>* lam, PauliAdjointArgs a, bitCapInt nItems,
+    double* partialsRe, double* partialsIm)
+{
+    double re = 0, im = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    const R c = (R)a.cs, s = (R)a.sn;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        unsigned p0, p1;
+        if constexpr (sizeof(R) == 4) {
+            float4* ps = reinterpret_cast<float4*>(psi);
+            float4* pl = reinterpret_cast<float4*>(lam);
+            float4 A = ld4<NT>(ps + v), P = ld4<NT>(pl + v);
+            pauliAdjointParity<true>(a.z, v << 1u, p0, p1);
+            pauliBraketDiag<float>(A.x, A.y, P.x, P.y, p0 ? -a.w : a.w, re, im);
+            pauliBraketDiag<float>(A.z, A.w, P.z, P.w, p1 ? -a.w : a.w, re, im);
+            const float s0 = p0 ? -s : s, s1 = p1 ? -s : s;
+            pauliEvolveScale<float>(c, -s0, A.x, A.y);
+            pauliEvolveScale<float>(c, -s1, A.z, A.w);
+            pauliEvolveScale<float>(c, -s0, P.x, P.y);
+            pauliEvolveScale<float>(c, -s1, P.z, P.w);
+            st4<NT>(ps + v, A);
+            st4<NT>(pl + v, P);
+        } else {
+            double2* ps = reinterpret_cast<double2*>(psi);
+            double2* pl = reinterpret_cast<double2*>(lam);
+            double2 A = ps[v], P = pl[v];
+            pauliAdjointParity<false>(a.z, v, p0, p1);
+            pauliBraketDiag<double>(A.x, A.y, P.x, P.y, p0 ? -a.w : a.w, re, im);
+            const double s0 = p0 ? -s : s;
+            pauliEvolveScale<double>(c, -s0, A.x, A.y);
+            pauliEvolveScale<double>(c, -s0, P.x, P.y);
+            ps[v] = A;
+            pl[v] = P;
+        }
+    }
+    blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
+}
+
+template <typename R, bool NT>
+static void launchPauliAdjointNt(cplx<R>* psi, cplx<R>* lam, const PauliAdjointArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream)
+{
+    bitCapInt nItems, topPow;
+    const int mode = pauliPairMode<R>(a.x, a.nAmps, nItems, topPow);
+    const int grid = gridForPairs(nItems);
+    double* pRe = partialsDev;
+    double* pIm = partialsDev + QA_REDUCE_MAX_BLOCKS;
+    const dim3 g(grid), b(QA_BLOCK);
+    if (mode < 0) {
+        hipLaunchKernelGGL((k_pauli_adjoint_diag<R, NT>), g, b, 0, stream, psi, lam, a, nItems, pRe, pIm);
+    } else if constexpr (sizeof(R) == 4) {
+        if (mode == 2) {
+            hipLaunchKernelGGL(
+                (k_pauli_adjoint<R, 2, NT>), g, b, 0, stream, psi, lam, a, nItems, topPow, pRe, pIm);
+        } else {
+            hipLaunchKernelGGL(
+                (k_pauli_adjoint<R, 1, NT>), g, b, 0, stream, psi, lam, a, nItems, topPow, pRe, pIm);
+        }
+    } else {
+        hipLaunchKernelGGL((k_pauli_adjoint<R, 0, NT>), g, b, 0, stream, psi, lam, a, nItems, topPow, pRe, pIm);
+    }
+    hipLaunchKernelGGL(k_pauli_finish2, dim3(1), dim3(QA_BLOCK), 0, stream, pRe, pIm, grid, resultDev);
+}
+
+template <typename R>
+void launchPauliAdjoint(cplx<R>* psi, cplx<R>* lam, const PauliAdjointArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream)
+{
+    // nontemporal access exists for the float4 streams only
+    if constexpr (sizeof(R) == 4) {
+        if (useNontemporal()) {
+            launchPauliAdjointNt<R, true>(psi, lam, a, partialsDev, resultDev, stream);
+            return;
+        }
+    }
+    launchPauliAdjointNt<R, false>(psi, lam, a, partialsDev, resultDev, stream);
+}
+
 // ---- reduced density matrices -----------------------------------------------------
 //
 // rho[a,b] = sum_e psi[e,a] conj(psi[e,b]) over the kept qubits in ascending
@@ -4123,6 +4662,12 @@ void launchRdmTile(const cplx<R>* sv, int kt, const RdmTileArgs& a, double* part
     template int launchArgMax<R>(const cplx<R>*, bitCapInt, double*, bitCapInt*, hipStream_t);      \
     template void launchPauliGroup<R>(const cplx<R>*, const PauliArgs&, double*, double*, hipStream_t); \
     template void launchPauliEvolve<R>(cplx<R>*, const PauliEvolveArgs&, hipStream_t);              \
+    template void launchPauliBraket<R>(                                                             \
+        const cplx<R>*, const cplx<R>*, const PauliArgs&, double, double*, double*, hipStream_t);   \
+    template void launchPauliApply<R>(                                                              \
+        const cplx<R>*, cplx<R>*, const PauliArgs&, double, bool, hipStream_t);                     \
+    template void launchPauliAdjoint<R>(                                                            \
+        cplx<R>*, cplx<R>*, const PauliAdjointArgs&, double*, double*, hipStream_t);                \
     template void launchRdmReg<R>(                                                                  \
         const cplx<R>*, int, bool, const RdmRegArgs&, double*, double*, hipStream_t);               \
     template void launchRdmTile<R>(                                                                 \

@@ -137,6 +137,20 @@ struct PauliEvolveArgs {
     double w[QA_PAULI_MAX_TERMS];
 };
 
+// One fused step of the adjoint-gradient sweep for the rotation
+// exp(-i theta P) of ONE string P = i^ny (-1)^popcount(i&z) |i^x><i|: the
+// launch sums <lam|P|psi> and applies exp(+i theta P) to both vectors. w is
+// the real factor of i^ny (+1 or -1) and im says whether a factor i remains;
+// cs / sn are the host's cos / sin of -theta * w, as segCos / segSin are.
+struct PauliAdjointArgs {
+    bitCapInt x;     // X/Y mask; 0 selects the diagonal kernel
+    bitCapInt z;
+    bitCapInt nAmps; // 2^qubits
+    int im;
+    double w;
+    double cs, sn;
+};
+
 // reduced density matrix, register regime (rdm_plan.hpp): kept powers
 // ascending, and the state offset of every kept index in that order
 struct RdmRegArgs {
@@ -184,6 +198,26 @@ void launchPauliEvolve(cplx<R>* sv, const PauliEvolveArgs& a, hipStream_t stream
 // order into *resultDev. Reads sv only.
 template <typename R>
 void launchPauliGroup(const cplx<R>* sv, const PauliArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream);
+
+// The three pair-walk launches below use the reduction grid, capped by
+// QRACK_GPU_BLOCKS when that is set. partialsDev holds 2 * QA_REDUCE_MAX_BLOCKS
+// doubles (real parts, then imaginary parts); resultDev takes (re, im).
+
+// <bra| ident + sum_t w_t P_t |psi> for one group; reads both vectors only
+template <typename R>
+void launchPauliBraket(const cplx<R>* psi, const cplx<R>* bra, const PauliArgs& a, double ident,
+    double* partialsDev, double* resultDev, hipStream_t stream);
+
+// dest = (ident + sum_t w_t P_t) psi when `first` (dest is not read), else
+// dest += (sum_t w_t P_t) psi. dest must not alias psi.
+template <typename R>
+void launchPauliApply(const cplx<R>* psi, cplx<R>* dest, const PauliArgs& a, double ident, bool first,
+    hipStream_t stream);
+
+// resultDev <- <lam|P|psi>, then psi and lam <- exp(+i theta P) of themselves
+template <typename R>
+void launchPauliAdjoint(cplx<R>* psi, cplx<R>* lam, const PauliAdjointArgs& a, double* partialsDev,
     double* resultDev, hipStream_t stream);
 
 template <typename R>

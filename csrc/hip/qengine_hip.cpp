@@ -157,6 +157,7 @@ template <typename R> QEngineHIP<R>::~QEngineHIP()
     releaseTileSums();
     releaseAux();
     releaseRdm();
+    releasePairResults();
     if (dPartials) hipFree(dPartials);
     if (dIdx) hipFree(dIdx);
     hipStreamDestroy(stream);
@@ -341,6 +342,7 @@ template <typename R> void QEngineHIP<R>::SetDevice(int64_t devId)
     releaseTileSums();
     releaseAux();
     releaseRdm();
+    releasePairResults();
     freeDev(dState_, maxQPower);
     hipStreamDestroy(stream);
     hipFree(dPartials);
@@ -1275,18 +1277,16 @@ template <typename R> double QEngineHIP<R>::reduceSum(int op, const ReduceArgs& 
 
 // ---- Pauli strings and sums -------------------------------------------------
 
-template <typename R> double QEngineHIP<R>::pauliGroupsSum(const std::vector<PauliGroup>& groups)
+// One launch per (group, chunk of QA_PAULI_MAX_TERMS terms), groups in order
+static std::vector<PauliArgs> pauliChunkLaunches(const std::vector<PauliGroup>& groups, bitCapInt nAmps)
 {
-    // One launch per (group, chunk of QA_PAULI_MAX_TERMS terms). Each launch
-    // folds its block partials (first half of dPartials) into one double in
-    // the second half; the whole call's results come back in one copy.
     std::vector<PauliArgs> launches;
     for (const PauliGroup& g : groups) {
         size_t r = 0, m = 0;
         while (r < g.re.size() || m < g.im.size()) {
             PauliArgs a{};
             a.x = g.x;
-            a.nAmps = maxQPower;
+            a.nAmps = nAmps;
             while (a.nTerms < QA_PAULI_MAX_TERMS && r < g.re.size()) {
                 a.z[a.nTerms] = g.re[r].z;
                 a.w[a.nTerms++] = g.re[r++].w;
@@ -1299,6 +1299,14 @@ template <typename R> double QEngineHIP<R>::pauliGroupsSum(const std::vector<Pau
             launches.push_back(a);
         }
     }
+    return launches;
+}
+
+template <typename R> double QEngineHIP<R>::pauliGroupsSum(const std::vector<PauliGroup>& groups)
+{
+    // Each launch folds its block partials (first half of dPartials) into one
+    // double in the second half; the whole call's results come back in one copy.
+    const std::vector<PauliArgs> launches = pauliChunkLaunches(groups, maxQPower);
     if (launches.empty()) return 0.0;
     QA_HIP_CHECK(hipSetDevice(deviceId));
     HipProfScope prof("pauli", stream);
@@ -1602,6 +1610,226 @@ void QEngineHIP<R>::EvolvePauliSum(
 {
     const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "EvolvePauliSum");
     pauliEvolveRun(c, pauliEvolvePlan(c, time, steps, order));
+}
+
+// ---- Pauli brakets, H|psi>, adjoint gradient -----------------------------------
+
+template <typename R> void QEngineHIP<R>::releasePairResults()
+{
+    if (dPairRes_) hipFree(dPairRes_);
+    dPairRes_ = nullptr;
+    pairResLen_ = 0;
+}
+
+template <typename R> double* QEngineHIP<R>::pairResults(size_t n)
+{
+    if (n <= pairResLen_) return dPairRes_;
+    QA_HIP_CHECK(hipStreamSynchronize(stream)); // nothing still writes the old slots
+    releasePairResults();
+    QA_HIP_CHECK(hipMalloc(&dPairRes_, 2u * n * sizeof(double)));
+    pairResLen_ = n;
+    return dPairRes_;
+}
+
+namespace {
+// the launches of a canonical sum; a sum without non-identity terms is one
+// diagonal launch with an empty table
+std::vector<PauliArgs> pauliSumLaunches(const PauliCanonSum& c, bitCapInt nAmps)
+{
+    std::vector<PauliArgs> launches = pauliChunkLaunches(c.groups, nAmps);
+    if (launches.empty()) {
+        PauliArgs a{};
+        a.nAmps = nAmps;
+        launches.push_back(a);
+    }
+    return launches;
+}
+} // namespace
+
+template <typename R>
+cplx<double> QEngineHIP<R>::PauliSumBraket(QInterfacePtr<R> bra, const std::vector<PauliTerm>& terms)
+{
+    if (bra->GetQubitCount() != qubitCount) throw QrackError("PauliSumBraket: width mismatch");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "PauliSumBraket");
+    const std::vector<PauliArgs> launches = pauliSumLaunches(c, maxQPower);
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    // a staged copy of the bra is freed on every way out
+    struct Staged {
+        QEngineHIP<R>* self;
+        cplx<R>* p = nullptr;
+        ~Staged() { self->freeDev(p, self->maxQPower); }
+    } staged{ this };
+    QEngineHIP<R>* o = dynamic_cast<QEngineHIP<R>*>(bra.get());
+    const cplx<R>* braBuf = nullptr;
+    if (o == this) {
+        braBuf = rState();
+    } else if (o && o->deviceId == deviceId) {
+        braBuf = o->rState();
+        o->Finish();
+    } else {
+        std::vector<cplx<R>> host(maxQPower);
+        bra->GetQuantumState(host.data());
+        staged.p = allocDev(maxQPower);
+        QA_HIP_CHECK(hipMemcpyAsync(
+            staged.p, host.data(), sizeof(cplx<R>) * maxQPower, hipMemcpyHostToDevice, stream));
+        QA_HIP_CHECK(hipStreamSynchronize(stream)); // host goes out of scope
+        braBuf = staged.p;
+    }
+    const cplx<R>* sv = rState();
+    double* dRes = pairResults(launches.size());
+    std::vector<double> hRes(2u * launches.size());
+    {
+        HipProfScope prof("pauli_braket", stream);
+        // the identity's share rides on the first launch: both vectors are in hand
+        for (size_t k = 0; k < launches.size(); ++k) {
+            launchPauliBraket<R>(
+                sv, braBuf, launches[k], k ? 0.0 : c.identity, dPartials, dRes + 2u * k, stream);
+        }
+        QA_HIP_CHECK(hipMemcpyAsync(
+            hRes.data(), dRes, hRes.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        Finish();
+    }
+    double re = 0, im = 0;
+    for (size_t k = 0; k < launches.size(); ++k) {
+        re += hRes[2u * k];
+        im += hRes[2u * k + 1u];
+    }
+    return cplx<double>(re, im);
+}
+
+template <typename R>
+void QEngineHIP<R>::pauliApplyRun(const PauliCanonSum& c, const cplx<R>* src, cplx<R>* dst)
+{
+    const std::vector<PauliArgs> launches = pauliSumLaunches(c, maxQPower);
+    for (size_t k = 0; k < launches.size(); ++k) {
+        HipProfScope prof("pauli_apply", stream);
+        launchPauliApply<R>(src, dst, launches[k], c.identity, k == 0u, stream);
+    }
+}
+
+template <typename R>
+void QEngineHIP<R>::PauliSumApplyInto(const std::vector<PauliTerm>& terms, QInterfacePtr<R> dest)
+{
+    if (dest.get() == this) throw QrackError("PauliSumApplyInto: dest is this simulator");
+    if (dest->GetQubitCount() != qubitCount) throw QrackError("PauliSumApplyInto: width mismatch");
+    QEngineHIP<R>* d = dynamic_cast<QEngineHIP<R>*>(dest.get());
+    if (!d || d->deviceId != deviceId)
+        throw QrackError("PauliSumApplyInto: dest must be a HIP engine on the same device");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "PauliSumApplyInto");
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    d->Finish(); // whatever dest still had queued on its own stream
+    const cplx<R>* src = rState();
+    pauliApplyRun(c, src, d->wStateAll());
+    Finish(); // dest's stream may use the buffer from here on
+    d->runningNorm = (R)-1;
+}
+
+template <typename R>
+void QEngineHIP<R>::pauliRotateBuffer(cplx<R>* buf, const PauliGroup& g, double angle)
+{
+    const bool isIm = !g.im.empty();
+    const PauliCanonTerm t = isIm ? g.im[0] : g.re[0];
+    PauliEvolveArgs a{};
+    a.x = g.x;
+    a.nAmps = maxQPower;
+    a.nSeg = 1;
+    a.segEnd[0] = 1;
+    a.segIm[0] = isIm ? 1 : 0;
+    a.z[0] = t.z;
+    a.w[0] = angle * t.w;
+    a.segCos[0] = std::cos(a.w[0]);
+    a.segSin[0] = std::sin(a.w[0]);
+    HipProfScope prof("pauli_evolve", stream);
+    launchPauliEvolve<R>(buf, a, stream);
+}
+
+template <typename R>
+double QEngineHIP<R>::AdjointGradient(const std::vector<AdjointOp<R>>& ops,
+    const std::vector<PauliTerm>& terms, std::vector<double>& grad)
+{
+    validateAdjointOps(ops, qubitCount);
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "AdjointGradient");
+    grad.clear();
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    size_t nTrain = 0;
+    for (const AdjointOp<R>& op : ops) {
+        if (op.kind == AdjointOp<R>::Rotation && op.trainable) ++nTrain;
+    }
+    // slot 0: <lambda|psi_N>; slot 1 + t: <lambda|P|psi> of trainable rotation t
+    double* dRes = pairResults(nTrain + 1u);
+    // the second vector: a raw buffer the allocation cap counts, freed on
+    // every way out. Taken before the state is touched, so that a refusal
+    // leaves psi_0 in place.
+    struct Lambda {
+        QEngineHIP<R>* self;
+        cplx<R>* p = nullptr;
+        ~Lambda() { self->freeDev(p, self->maxQPower); }
+    } lam{ this };
+    lam.p = allocDev(maxQPower);
+    for (const AdjointOp<R>& op : ops) {
+        if (op.kind == AdjointOp<R>::Rotation) {
+            PauliRotation(op.qubits, op.paulis, op.theta);
+        } else {
+            MtrxN(op.qubits, op.mtrx.data(), op.controls, op.anti);
+        }
+    }
+    pauliApplyRun(c, wState(), lam.p);
+    {
+        // E = Re <lambda|psi_N>: the braket of the identity alone
+        PauliArgs a{};
+        a.nAmps = maxQPower;
+        HipProfScope prof("pauli_braket", stream);
+        launchPauliBraket<R>(rState(), lam.p, a, 1.0, dPartials, dRes, stream);
+    }
+    // what a launcher of this engine does to the state, done to lambda
+    auto onLambda = [&](const std::function<void()>& f) {
+        std::swap(dState_, lam.p);
+        try {
+            f();
+        } catch (...) {
+            std::swap(dState_, lam.p);
+            throw;
+        }
+        std::swap(dState_, lam.p);
+    };
+    size_t slot = nTrain;
+    for (size_t k = ops.size(); k-- > 0u;) {
+        const AdjointOp<R>& op = ops[k];
+        if (op.kind == AdjointOp<R>::Gate) {
+            const std::vector<cplx<R>> dag = adjointOpDagger(op);
+            MtrxN(op.qubits, dag.data(), op.controls, op.anti);
+            onLambda([&] { MtrxN(op.qubits, dag.data(), op.controls, op.anti); });
+            continue;
+        }
+        bitCapInt x, z;
+        pauliStringMasks(op.qubits, op.paulis, qubitCount, x, z);
+        const PauliGroup g = pauliStringGroup(x, z, 1.0);
+        if (!op.trainable) {
+            pauliRotateBuffer(wState(), g, -op.theta);
+            pauliRotateBuffer(lam.p, g, -op.theta);
+            continue;
+        }
+        const bool isIm = !g.im.empty();
+        const PauliCanonTerm t = isIm ? g.im[0] : g.re[0];
+        PauliAdjointArgs a{};
+        a.x = x;
+        a.z = t.z;
+        a.nAmps = maxQPower;
+        a.im = isIm ? 1 : 0;
+        a.w = t.w;
+        a.cs = std::cos(-op.theta * t.w);
+        a.sn = std::sin(-op.theta * t.w);
+        HipProfScope prof("pauli_adjoint", stream);
+        launchPauliAdjoint<R>(wState(), lam.p, a, dPartials, dRes + 2u * slot, stream);
+        --slot;
+    }
+    std::vector<double> hRes(2u * (nTrain + 1u));
+    QA_HIP_CHECK(hipMemcpyAsync(
+        hRes.data(), dRes, hRes.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    Finish();
+    grad.resize(nTrain);
+    for (size_t t = 0; t < nTrain; ++t) grad[t] = 2.0 * hRes[2u * (t + 1u) + 1u];
+    return hRes[0];
 }
 
 template <typename R> std::pair<double, bitCapInt> QEngineHIP<R>::argMax()

@@ -221,6 +221,23 @@ public:
         double theta) override;
     void EvolvePauliSum(
         const std::vector<PauliTerm>& terms, double time, int steps = 1, int order = 1) override;
+    // <bra|H|this>: one read-only launch per (X/Y mask, chunk of terms) over
+    // both vectors, block partials folded on the device, one copy and one
+    // host sync per call. A bra that is no HIP engine on this device is staged
+    // as SumSqrDiff stages its operand.
+    cplx<double> PauliSumBraket(QInterfacePtr<R> bra, const std::vector<PauliTerm>& terms) override;
+    // dest <- H|this>: the same launches; the first writes dest, the rest
+    // accumulate into it. dest is a HIP engine on this device.
+    void PauliSumApplyInto(const std::vector<PauliTerm>& terms, QInterfacePtr<R> dest) override;
+    // Adjoint gradient with one extra state-sized buffer (peak: two states).
+    // Forward pass, lambda = H psi, then the backward sweep on one stream with
+    // no host sync: a trainable rotation is ONE fused launch over both
+    // vectors, everything else is the existing launch on each. The energy and
+    // every <lambda|P|psi> come back in one copy at the end. (A gate on more
+    // than 3 qubits stages its matrix through the aux buffer, which waits for
+    // the stream.)
+    double AdjointGradient(const std::vector<AdjointOp<R>>& ops, const std::vector<PauliTerm>& terms,
+        std::vector<double>& grad) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;
@@ -283,6 +300,14 @@ protected:
     double reduceSum(int op, const ReduceArgs& a);
     double pauliGroupsSum(const std::vector<PauliGroup>& groups);
     void pauliEvolveRun(const PauliCanonSum& c, const PauliEvolvePlan& plan);
+    // dst <- (identity + groups) src, one profiled launch per (group, chunk)
+    void pauliApplyRun(const PauliCanonSum& c, const cplx<R>* src, cplx<R>* dst);
+    // exp(-i angle P) for the one string of g on a raw buffer (a state or the
+    // adjoint sweep's second vector), through the evolution launcher
+    void pauliRotateBuffer(cplx<R>* buf, const PauliGroup& g, double angle);
+    // device slots for `n` (re, im) results of the pair-walk reductions
+    double* pairResults(size_t n);
+    void releasePairResults();
     // string with X/Y factors -> value; false when the generic lowering must answer
     bool pauliStringNative(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
         const char* what, double& value);
@@ -356,6 +381,8 @@ private:
     bool externView_ = false; // sticky: a raw pointer escaped this engine
     double* dRdm_ = nullptr;
     size_t rdmBytes_ = 0;
+    double* dPairRes_ = nullptr; // (re, im) per launch of a braket or gradient call
+    size_t pairResLen_ = 0;      // in results
 };
 
 } // namespace qrack_amd

@@ -837,6 +837,257 @@ void QEngineCPU<R>::EvolvePauliSum(
     pauliEvolveRun(c, pauliEvolvePlan(c, time, steps, order));
 }
 
+// ---- Pauli brakets, H|psi>, adjoint gradient ----------------------------------
+//
+// With W(i) = wr(i) + i wi(i) a group's summed weight at index i, the weight at
+// the partner i^x is conj(W(i)): re-set terms hold an even number of Y factors
+// and keep their sign across the pair, im-set terms flip it.
+
+namespace {
+// signed weight sums of one group at index i
+inline void pauliGroupWeights(const PauliCanonTerm* re, size_t nRe, const PauliCanonTerm* im, size_t nIm,
+    bitCapInt i, double& wr, double& wi)
+{
+    wr = 0;
+    wi = 0;
+    for (size_t t = 0; t < nRe; ++t) wr += __builtin_parityll(i & re[t].z) ? -re[t].w : re[t].w;
+    for (size_t t = 0; t < nIm; ++t) wi += __builtin_parityll(i & im[t].z) ? -im[t].w : im[t].w;
+}
+} // namespace
+
+template <typename R>
+cplx<double> QEngineCPU<R>::pauliBraketRun(const PauliCanonSum& c, const cplx<R>* bra, const cplx<R>* sv)
+{
+    double totRe = 0, totIm = 0;
+    // the identity's share rides on the first sweep: both vectors are in hand
+    bool identPending = true;
+    auto sweep = [&](const PauliGroup& g) {
+        const PauliCanonTerm* re = g.re.data();
+        const PauliCanonTerm* im = g.im.data();
+        const size_t nRe = g.re.size(), nIm = g.im.size();
+        const double id = identPending ? c.identity : 0.0;
+        identPending = false;
+        double r = 0, m = 0;
+        if (!g.x) {
+            this->par_sum2(maxQPower, [=](const bitCapInt& i, double& ar, double& ai) {
+                double wr, wi;
+                pauliGroupWeights(re, nRe, im, 0, i, wr, wi);
+                wr += id;
+                const cplx<R> a = sv[i], p = bra[i];
+                ar += wr * (double)(p.re * a.re + p.im * a.im);
+                ai += wr * (double)(p.re * a.im - p.im * a.re);
+            }, r, m);
+        } else {
+            const bitCapInt x = g.x;
+            const bitCapInt topPow = pow2(log2Ocl(x));
+            this->par_sum2(maxQPower >> 1u, [=](const bitCapInt& j, double& ar, double& ai) {
+                const bitCapInt i = insertZeroBit(j, topPow);
+                double wr, wi;
+                pauliGroupWeights(re, nRe, im, nIm, i, wr, wi);
+                const cplx<R> a = sv[i], b = sv[i ^ x], p = bra[i], q = bra[i ^ x];
+                const R t1r = q.re * a.re + q.im * a.im, t1i = q.re * a.im - q.im * a.re;
+                const R t2r = p.re * b.re + p.im * b.im, t2i = p.re * b.im - p.im * b.re;
+                ar += wr * ((double)t1r + (double)t2r) - wi * ((double)t1i - (double)t2i);
+                ai += wr * ((double)t1i + (double)t2i) + wi * ((double)t1r - (double)t2r);
+                if (id != 0) {
+                    ar += id * ((double)(p.re * a.re + p.im * a.im) + (double)(q.re * b.re + q.im * b.im));
+                    ai += id * ((double)(p.re * a.im - p.im * a.re) + (double)(q.re * b.im - q.im * b.re));
+                }
+            }, r, m);
+        }
+        totRe += r;
+        totIm += m;
+    };
+    for (const PauliGroup& g : c.groups) sweep(g);
+    // nothing but identities: the plain inner product
+    if (identPending) sweep(PauliGroup{});
+    return cplx<double>(totRe, totIm);
+}
+
+template <typename R>
+void QEngineCPU<R>::pauliApplyRun(const PauliCanonSum& c, const cplx<R>* sv, cplx<R>* dest)
+{
+    // the first sweep writes dest without reading it and adds identity * psi
+    bool first = true;
+    auto sweep = [&](const PauliGroup& g) {
+        const PauliCanonTerm* re = g.re.data();
+        const PauliCanonTerm* im = g.im.data();
+        const size_t nRe = g.re.size(), nIm = g.im.size();
+        const bool isFirst = first;
+        const double id = c.identity;
+        first = false;
+        if (!g.x) {
+            this->par_for(0, maxQPower, [=](const bitCapInt& i, unsigned) {
+                double wr, wi;
+                pauliGroupWeights(re, nRe, im, 0, i, wr, wi);
+                if (isFirst) {
+                    dest[i] = (R)(wr + id) * sv[i];
+                } else {
+                    dest[i] = dest[i] + (R)wr * sv[i];
+                }
+            });
+            return;
+        }
+        const bitCapInt x = g.x;
+        const bitCapInt topPow = pow2(log2Ocl(x));
+        this->par_for(0, maxQPower >> 1u, [=](const bitCapInt& j, unsigned) {
+            const bitCapInt i = insertZeroBit(j, topPow);
+            double wr, wi;
+            pauliGroupWeights(re, nRe, im, nIm, i, wr, wi);
+            const cplx<R> a = sv[i], b = sv[i ^ x];
+            const cplx<R> w((R)wr, (R)wi);
+            cplx<R> da, db;
+            if (isFirst) {
+                da = (R)id * a;
+                db = (R)id * b;
+            } else {
+                da = dest[i];
+                db = dest[i ^ x];
+            }
+            dest[i] = da + conj(w) * b;
+            dest[i ^ x] = db + w * a;
+        });
+    };
+    for (const PauliGroup& g : c.groups) sweep(g);
+    if (first) sweep(PauliGroup{});
+}
+
+template <typename R>
+cplx<double> QEngineCPU<R>::pauliAdjointStep(const PauliGroup& g, double angle, cplx<R>* sv, cplx<R>* lam)
+{
+    const bool isIm = !g.im.empty();
+    const PauliCanonTerm t = isIm ? g.im[0] : g.re[0];
+    const bitCapInt z = t.z;
+    const double w = t.w;
+    const R cs = (R)std::cos(angle * w), sn = (R)std::sin(angle * w);
+    double r = 0, m = 0;
+    if (!g.x) {
+        this->par_sum2(maxQPower, [=](const bitCapInt& i, double& ar, double& ai) {
+            const bool odd = __builtin_parityll(i & z);
+            const double wi = odd ? -w : w;
+            const cplx<R> a = sv[i], p = lam[i];
+            ar += wi * (double)(p.re * a.re + p.im * a.im);
+            ai += wi * (double)(p.re * a.im - p.im * a.re);
+            const cplx<R> ph(cs, odd ? sn : -sn);
+            sv[i] = ph * a;
+            lam[i] = ph * p;
+        }, r, m);
+        return cplx<double>(r, m);
+    }
+    const bitCapInt x = g.x;
+    const bitCapInt topPow = pow2(log2Ocl(x));
+    this->par_sum2(maxQPower >> 1u, [=](const bitCapInt& j, double& ar, double& ai) {
+        const bitCapInt i = insertZeroBit(j, topPow);
+        const bool odd = __builtin_parityll(i & z);
+        const double wi = odd ? -w : w;
+        const R s = odd ? -sn : sn;
+        cplx<R> a = sv[i], b = sv[i ^ x], p = lam[i], q = lam[i ^ x];
+        const R t1r = q.re * a.re + q.im * a.im, t1i = q.re * a.im - q.im * a.re;
+        const R t2r = p.re * b.re + p.im * b.im, t2i = p.re * b.im - p.im * b.re;
+        if (isIm) {
+            ar -= wi * ((double)t1i - (double)t2i);
+            ai += wi * ((double)t1r - (double)t2r);
+        } else {
+            ar += wi * ((double)t1r + (double)t2r);
+            ai += wi * ((double)t1i + (double)t2i);
+        }
+        auto rot = [&](cplx<R>& u, cplx<R>& v) {
+            if (isIm) {
+                const cplx<R> nu(cs * u.re - s * v.re, cs * u.im - s * v.im);
+                v = cplx<R>(cs * v.re + s * u.re, cs * v.im + s * u.im);
+                u = nu;
+            } else {
+                const cplx<R> nu(cs * u.re + s * v.im, cs * u.im - s * v.re);
+                v = cplx<R>(cs * v.re + s * u.im, cs * v.im - s * u.re);
+                u = nu;
+            }
+        };
+        rot(a, b);
+        rot(p, q);
+        sv[i] = a;
+        sv[i ^ x] = b;
+        lam[i] = p;
+        lam[i ^ x] = q;
+    }, r, m);
+    return cplx<double>(r, m);
+}
+
+template <typename R>
+cplx<double> QEngineCPU<R>::PauliSumBraket(QInterfacePtr<R> bra, const std::vector<PauliTerm>& terms)
+{
+    if (bra->GetQubitCount() != qubitCount) throw QrackError("PauliSumBraket: width mismatch");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "PauliSumBraket");
+    QEngineCPU<R>* o = dynamic_cast<QEngineCPU<R>*>(bra.get());
+    std::vector<cplx<R>> tmp;
+    const cplx<R>* bv;
+    if (o) {
+        bv = o->stateVec.data();
+    } else {
+        tmp.resize(maxQPower);
+        bra->GetQuantumState(tmp.data());
+        bv = tmp.data();
+    }
+    return pauliBraketRun(c, bv, stateVec.data());
+}
+
+template <typename R>
+void QEngineCPU<R>::PauliSumApplyInto(const std::vector<PauliTerm>& terms, QInterfacePtr<R> dest)
+{
+    if (dest.get() == this) throw QrackError("PauliSumApplyInto: dest is this simulator");
+    if (dest->GetQubitCount() != qubitCount) throw QrackError("PauliSumApplyInto: width mismatch");
+    QEngineCPU<R>* d = dynamic_cast<QEngineCPU<R>*>(dest.get());
+    if (!d) throw QrackError("PauliSumApplyInto: dest must be a CPU engine like this one");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "PauliSumApplyInto");
+    pauliApplyRun(c, stateVec.data(), d->stateVec.data());
+    d->runningNorm = (R)-1;
+}
+
+template <typename R>
+double QEngineCPU<R>::AdjointGradient(const std::vector<AdjointOp<R>>& ops,
+    const std::vector<PauliTerm>& terms, std::vector<double>& grad)
+{
+    validateAdjointOps(ops, qubitCount);
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "AdjointGradient");
+    grad.clear();
+    for (const AdjointOp<R>& op : ops) {
+        if (op.kind == AdjointOp<R>::Rotation) {
+            PauliRotation(op.qubits, op.paulis, op.theta);
+        } else {
+            MtrxN(op.qubits, op.mtrx.data(), op.controls, op.anti);
+        }
+    }
+    // lambda = H psi_N, and E = Re <lambda|psi_N>
+    std::vector<cplx<R>> lam(maxQPower);
+    pauliApplyRun(c, stateVec.data(), lam.data());
+    PauliCanonSum one;
+    one.identity = 1.0;
+    const double energy = pauliBraketRun(one, lam.data(), stateVec.data()).re;
+    // sweep back: what applies to the state applies to lambda through a swap
+    auto onBoth = [&](const std::function<void()>& f) {
+        f();
+        stateVec.swap(lam);
+        f();
+        stateVec.swap(lam);
+    };
+    for (size_t k = ops.size(); k-- > 0u;) {
+        const AdjointOp<R>& op = ops[k];
+        if (op.kind == AdjointOp<R>::Gate) {
+            const std::vector<cplx<R>> dag = adjointOpDagger(op);
+            onBoth([&] { MtrxN(op.qubits, dag.data(), op.controls, op.anti); });
+        } else if (!op.trainable) {
+            onBoth([&] { PauliRotation(op.qubits, op.paulis, -op.theta); });
+        } else {
+            bitCapInt x, z;
+            pauliStringMasks(op.qubits, op.paulis, qubitCount, x, z);
+            const cplx<double> b
+                = pauliAdjointStep(pauliStringGroup(x, z, 1.0), -op.theta, stateVec.data(), lam.data());
+            grad.push_back(2.0 * b.im);
+        }
+    }
+    std::reverse(grad.begin(), grad.end());
+    return energy;
+}
+
 template <typename R> bool QEngineCPU<R>::ForceMParity(bitCapInt mask, bool result, bool doForce)
 {
     if (!mask) return false;

@@ -109,6 +109,13 @@ public:
         double theta) override;
     void EvolvePauliSum(
         const std::vector<PauliTerm>& terms, double time, int steps = 1, int order = 1) override;
+    // Brakets, H|psi> and the adjoint gradient: the pair walk of the Pauli
+    // sums, one sweep per X/Y mask; complex sums are private per worker and
+    // added in worker order. The gradient keeps one second amplitude array.
+    cplx<double> PauliSumBraket(QInterfacePtr<R> bra, const std::vector<PauliTerm>& terms) override;
+    void PauliSumApplyInto(const std::vector<PauliTerm>& terms, QInterfacePtr<R> dest) override;
+    double AdjointGradient(const std::vector<AdjointOp<R>>& ops, const std::vector<PauliTerm>& terms,
+        std::vector<double>& grad) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;
@@ -175,6 +182,10 @@ protected:
     void QftColumn(bitLenInt start, bitLenInt col, int sign, bool pre);
     double pauliGroupSum(const PauliGroup& g);
     void pauliEvolveRun(const PauliCanonSum& c, const PauliEvolvePlan& plan);
+    cplx<double> pauliBraketRun(const PauliCanonSum& c, const cplx<R>* bra, const cplx<R>* psi);
+    void pauliApplyRun(const PauliCanonSum& c, const cplx<R>* psi, cplx<R>* dest);
+    // <lam|P|psi> for the one string of g, then exp(-i angle P) on both arrays
+    cplx<double> pauliAdjointStep(const PauliGroup& g, double angle, cplx<R>* psi, cplx<R>* lam);
     bool pauliStringNative(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
         const char* what, double& value);
 

@@ -212,6 +212,28 @@ public:
         FlushAll();
         inner->EvolvePauliSum(t, time, steps, order);
     }
+    cplx<double> PauliSumBraket(QInterfacePtr<R> bra, const std::vector<PauliTerm>& t) override
+    {
+        FlushAll();
+        if (auto* of = dynamic_cast<QFuser<R>*>(bra.get())) of->FlushAll();
+        QInterfaceWrapper<R>* w = dynamic_cast<QInterfaceWrapper<R>*>(bra.get());
+        return inner->PauliSumBraket(w ? w->Inner() : bra, t);
+    }
+    void PauliSumApplyInto(const std::vector<PauliTerm>& t, QInterfacePtr<R> dest) override
+    {
+        if (dest.get() == this) throw QrackError("PauliSumApplyInto: dest is this simulator");
+        FlushAll();
+        // gates still pending in dest would land on the new state
+        if (auto* of = dynamic_cast<QFuser<R>*>(dest.get())) of->FlushAll();
+        QInterfaceWrapper<R>* w = dynamic_cast<QInterfaceWrapper<R>*>(dest.get());
+        inner->PauliSumApplyInto(t, w ? w->Inner() : dest);
+    }
+    double AdjointGradient(const std::vector<AdjointOp<R>>& ops, const std::vector<PauliTerm>& t,
+        std::vector<double>& grad) override
+    {
+        FlushAll();
+        return inner->AdjointGradient(ops, t, grad);
+    }
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override { FlushAll(); return inner->TrySeparate(q); }

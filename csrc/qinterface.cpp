@@ -5,6 +5,7 @@
 // for this build; engines override the hot paths with direct kernels.
 #include "qinterface.hpp"
 #include "qengine.hpp" // Pauli-sum canonical form and evolution plan
+#include "qengine_cpu.hpp" // AdjointGradient's default lowering runs on one
 
 #include <algorithm>
 #include <cstring>
@@ -762,6 +763,85 @@ void QInterface<R>::EvolvePauliSum(
             }
         }
     }
+}
+
+// ---- Pauli brakets, H|psi>, adjoint gradient: host-copy lowerings ------------
+
+// W(i) = sum over the group of coeff i^ny (-1)^popcount(i&z), in double
+static inline void pauliHostWeights(const PauliGroup& g, bitCapInt i, double& wr, double& wi)
+{
+    wr = 0;
+    wi = 0;
+    for (const PauliCanonTerm& t : g.re) wr += __builtin_parityll(i & t.z) ? -t.w : t.w;
+    for (const PauliCanonTerm& t : g.im) wi += __builtin_parityll(i & t.z) ? -t.w : t.w;
+}
+
+template <typename R>
+cplx<double> QInterface<R>::PauliSumBraket(QInterfacePtr<R> bra, const std::vector<PauliTerm>& terms)
+{
+    if (bra->GetQubitCount() != qubitCount) throw QrackError("PauliSumBraket: width mismatch");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "PauliSumBraket");
+    if (qubitCount > 26u) throw QrackError("PauliSumBraket: dense fallback width cap");
+    std::vector<cplx<R>> sv(maxQPower), bv(maxQPower);
+    GetQuantumState(sv.data());
+    bra->GetQuantumState(bv.data());
+    // <bra|P|psi> = sum_i W(i) conj(bra[i^x]) psi[i]
+    double re = 0, im = 0;
+    auto add = [&](bitCapInt i, bitCapInt x, double wr, double wi) {
+        const cplx<R> a = sv[i], q = bv[i ^ x];
+        const double tr = (double)(q.re * a.re + q.im * a.im), ti = (double)(q.re * a.im - q.im * a.re);
+        re += wr * tr - wi * ti;
+        im += wr * ti + wi * tr;
+    };
+    if (c.identity != 0) {
+        for (bitCapInt i = 0; i < maxQPower; ++i) add(i, 0u, c.identity, 0.0);
+    }
+    for (const PauliGroup& g : c.groups) {
+        for (bitCapInt i = 0; i < maxQPower; ++i) {
+            double wr, wi;
+            pauliHostWeights(g, i, wr, wi);
+            add(i, g.x, wr, wi);
+        }
+    }
+    return cplx<double>(re, im);
+}
+
+template <typename R>
+void QInterface<R>::PauliSumApplyInto(const std::vector<PauliTerm>& terms, QInterfacePtr<R> dest)
+{
+    if (dest.get() == this) throw QrackError("PauliSumApplyInto: dest is this simulator");
+    if (dest->GetQubitCount() != qubitCount) throw QrackError("PauliSumApplyInto: width mismatch");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "PauliSumApplyInto");
+    if (qubitCount > 26u) throw QrackError("PauliSumApplyInto: dense fallback width cap");
+    std::vector<cplx<R>> sv(maxQPower), out(maxQPower);
+    GetQuantumState(sv.data());
+    // (H psi)[k] = identity psi[k] + sum_g W_g(k^x_g) psi[k^x_g], summed in double
+    for (bitCapInt k = 0; k < maxQPower; ++k) {
+        double re = c.identity * (double)sv[k].re, im = c.identity * (double)sv[k].im;
+        for (const PauliGroup& g : c.groups) {
+            const bitCapInt i = k ^ g.x;
+            double wr, wi;
+            pauliHostWeights(g, i, wr, wi);
+            re += wr * (double)sv[i].re - wi * (double)sv[i].im;
+            im += wr * (double)sv[i].im + wi * (double)sv[i].re;
+        }
+        out[k] = cplx<R>((R)re, (R)im);
+    }
+    dest->SetQuantumState(out.data());
+}
+
+template <typename R>
+double QInterface<R>::AdjointGradient(const std::vector<AdjointOp<R>>& ops,
+    const std::vector<PauliTerm>& terms, std::vector<double>& grad)
+{
+    validateAdjointOps(ops, qubitCount);
+    validatePauliTerms(terms, qubitCount, "AdjointGradient");
+    if (qubitCount > 26u) throw QrackError("AdjointGradient: dense fallback width cap");
+    std::vector<cplx<R>> sv(maxQPower);
+    GetQuantumState(sv.data());
+    auto engine = std::make_shared<QEngineCPU<R>>(qubitCount, 0u, nullptr, false);
+    engine->SetQuantumState(sv.data());
+    return engine->AdjointGradient(ops, terms, grad);
 }
 
 // ---- ALU defaults ----------------------------------------------------------

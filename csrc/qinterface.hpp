@@ -153,6 +153,47 @@ inline void mtrxNHostApply(cplx<R>* sv, const std::vector<bitLenInt>& qubits, co
 template <typename R> class QInterface;
 template <typename R> using QInterfacePtr = std::shared_ptr<QInterface<R>>;
 
+// One factor of the circuit AdjointGradient differentiates: a Pauli rotation
+// exp(-i theta P) (PauliRotation's arguments) or a fixed dense gate (MtrxN's).
+template <typename R> struct AdjointOp {
+    enum Kind { Rotation, Gate } kind = Rotation;
+    std::vector<bitLenInt> qubits;
+    std::vector<Pauli> paulis;      // Rotation
+    double theta = 0;               // Rotation
+    bool trainable = true;          // Rotation
+    std::vector<cplx<R>> mtrx;      // Gate: row-major 2^k x 2^k, MtrxN convention, must be unitary
+    std::vector<bitLenInt> controls; // Gate
+    bool anti = false;              // Gate
+};
+
+// Argument check of AdjointGradient's op list, shared by every implementation
+template <typename R>
+inline void validateAdjointOps(const std::vector<AdjointOp<R>>& ops, bitLenInt qubitCount)
+{
+    for (const AdjointOp<R>& op : ops) {
+        if (op.kind == AdjointOp<R>::Rotation) {
+            validatePauliTerms({ PauliTerm{ 1.0, op.qubits, op.paulis } }, qubitCount, "AdjointGradient");
+        } else if (op.kind == AdjointOp<R>::Gate) {
+            validateMtrxN(op.qubits, op.controls, qubitCount);
+            const size_t D = (size_t)1 << op.qubits.size();
+            if (op.mtrx.size() != D * D) throw QrackError("AdjointGradient: gate matrix needs 4^k entries");
+        } else {
+            throw QrackError("AdjointGradient: bad op kind");
+        }
+    }
+}
+
+// conjugate transpose of a gate's matrix: what un-applies a unitary gate
+template <typename R> inline std::vector<cplx<R>> adjointOpDagger(const AdjointOp<R>& op)
+{
+    const size_t D = (size_t)1 << op.qubits.size();
+    std::vector<cplx<R>> d(D * D);
+    for (size_t r = 0; r < D; ++r) {
+        for (size_t c = 0; c < D; ++c) d[r * D + c] = conj(op.mtrx[c * D + r]);
+    }
+    return d;
+}
+
 // A term of a Trotterized Hamiltonian: (anti-)controlled 2x2 Hermitian op.
 // Parity target: /root/reference/include/hamiltonian.hpp:29-95.
 template <typename R> struct HamiltonianOp {
@@ -874,6 +915,35 @@ public:
     // pass per X/Y mask. order must be 1 or 2 and steps >= 1.
     virtual void EvolvePauliSum(
         const std::vector<PauliTerm>& terms, double time, int steps = 1, int order = 1);
+    // <bra|H|this> for H = sum_t coeff_t P_t: linear in this state,
+    // conjugate-linear in bra. Reads both operands and modifies neither; they
+    // may have any norms and may be the same object (the result is then
+    // ExpectationPauliSum, imaginary part zero to rounding). All-identity
+    // terms contribute their coefficient times <bra|this>. Throws QrackError
+    // on a width mismatch and on what ExpectationPauliSum throws on. Default
+    // lowering: host copies of both states (at most 26 qubits); the dense
+    // engines walk each X/Y mask's pairs once.
+    virtual cplx<double> PauliSumBraket(QInterfacePtr<R> bra, const std::vector<PauliTerm>& terms);
+    // dest <- H|this>, unnormalised; this state is untouched. dest has the
+    // same width, layer type and precision, and is not this object. dest's
+    // running norm is left unknown and nothing here normalises it.
+    virtual void PauliSumApplyInto(const std::vector<PauliTerm>& terms, QInterfacePtr<R> dest);
+    // Adjoint-method gradient. On entry the simulator holds psi_0. The call
+    // applies ops in order (PauliRotation or MtrxN), so U = U_N ... U_1, and
+    // returns E = <psi_N|H|psi_N>. grad gets dE/dtheta_k for every trainable
+    // rotation, in op order; a parameter shared by several ops is the
+    // caller's sum. With lambda_k = U_{k+1}^+ ... U_N^+ H psi_N,
+    //   dE/dtheta_k = 2 Im <lambda_k| P_k |psi_k>,
+    // and the sweep k = N..1 un-applies each op from both vectors (a gate by
+    // its conjugate transpose, a rotation by -theta), so one extra state is
+    // all it takes. On return the simulator holds psi_0 again, to rounding
+    // and not to the bit. Gate matrices are NOT checked for unitarity: a
+    // non-unitary gate gives a meaningless gradient and does not restore
+    // psi_0. Empty ops: the plain energy and an empty grad. Default lowering:
+    // the state is copied into a CPU engine of the same width, which runs the
+    // call; the simulator itself is untouched.
+    virtual double AdjointGradient(const std::vector<AdjointOp<R>>& ops,
+        const std::vector<PauliTerm>& terms, std::vector<double>& grad);
     // product observable squares to identity: Var = 1 - E^2
     double PauliProductVariance(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis)
     {

@@ -55,6 +55,14 @@ public:
     {
         QInterface<R>::EvolvePauliSum(t, time, steps, order);
     }
+    // the sweep un-applies every op, which random noise channels do not allow;
+    // the two read-style calls (PauliSumBraket, PauliSumApplyInto) are the
+    // wrapper's plain forwards
+    double AdjointGradient(const std::vector<AdjointOp<R>>&, const std::vector<PauliTerm>&,
+        std::vector<double>&) override
+    {
+        throw QrackError("AdjointGradient: not defined under gate noise");
+    }
 
     void Mtrx(const cplx<R>* m, bitLenInt t) override
     {

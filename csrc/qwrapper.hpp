@@ -176,6 +176,22 @@ public:
     {
         inner->EvolvePauliSum(t, time, steps, order);
     }
+    cplx<double> PauliSumBraket(QInterfacePtr<R> bra, const std::vector<PauliTerm>& t) override
+    {
+        QInterfaceWrapper<R>* w = dynamic_cast<QInterfaceWrapper<R>*>(bra.get());
+        return inner->PauliSumBraket(w ? w->inner : bra, t);
+    }
+    void PauliSumApplyInto(const std::vector<PauliTerm>& t, QInterfacePtr<R> dest) override
+    {
+        if (dest.get() == this) throw QrackError("PauliSumApplyInto: dest is this simulator");
+        QInterfaceWrapper<R>* w = dynamic_cast<QInterfaceWrapper<R>*>(dest.get());
+        inner->PauliSumApplyInto(t, w ? w->inner : dest);
+    }
+    double AdjointGradient(const std::vector<AdjointOp<R>>& ops, const std::vector<PauliTerm>& t,
+        std::vector<double>& grad) override
+    {
+        return inner->AdjointGradient(ops, t, grad);
+    }
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override { return inner->TrySeparate(q); }

@@ -108,6 +108,16 @@ void qrack_pauli_rotation(quid sid, const int* paulis, const uint64_t* qs, uint6
 void qrack_evolve_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
     const uint64_t* termLens, const uint64_t* qs, const int* paulis, double time, int steps,
     int order);
+/* <bra|H|sid>, H laid out as for qrack_expectation_pauli_sum: linear in sid,
+ * conjugate-linear in bra (same width and precision; may be sid itself).
+ * Neither simulator is modified; *re and *im receive the value (0 on error,
+ * which qrack_get_error(sid) reports) */
+void qrack_pauli_sum_braket(quid sid, quid bra, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, double* re, double* im);
+/* dest <- H|sid>, unnormalised; sid is untouched. dest has sid's width, stack
+ * and precision and is not sid */
+void qrack_pauli_sum_apply_into(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, quid dest);
 
 /* QFT */
 void qrack_qft(quid sid, uint64_t start, uint64_t length);
