@@ -184,7 +184,16 @@ def run_clifford_t_nn(q, n, rng, depth):
                 q.cz(i, i + 1)
 
 
+def run_krylov(q, n, rng, depth):
+    """Krylov quench of a Heisenberg chain from the Neel state: one step of
+    `depth` (default 16) Lanczos vectors. Needs depth + 1 states of memory."""
+    q.set_permutation(sum(1 << i for i in range(0, n, 2)))
+    terms = [(1.0, [i, i + 1], [p, p]) for i in range(n - 1) for p in (1, 3, 2)]
+    q.krylov_evolve_pauli_sum(terms, 0.5, dim=depth or 16, steps=1)
+
+
 WORKLOADS = {
+    "krylov": run_krylov,
     "clifford_t_nn": run_clifford_t_nn,
     "qft": run_qft,
     "qft_cosmology": run_qft_cosmology,

@@ -599,6 +599,41 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
             "(\"gate\", qubits, matrix[, controls, anti]) for a fixed unitary (mtrx_n arguments; not "
             "checked for unitarity). The gradient has one entry per trainable rotation, in op "
             "order. On return the simulator holds its initial state again, to rounding")
+        .def("lanczos_tridiagonal",
+            [](QI& q, std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms,
+                int dim) {
+                std::vector<double> alpha, beta;
+                q.LanczosTridiagonal(pauliTermsFromTuples(terms, "lanczos_tridiagonal"), dim, alpha, beta);
+                py::array_t<double> a((py::ssize_t)alpha.size()), b((py::ssize_t)beta.size());
+                std::copy(alpha.begin(), alpha.end(), a.mutable_data());
+                std::copy(beta.begin(), beta.end(), b.mutable_data());
+                return py::make_tuple(a, b);
+            },
+            py::arg("terms"), py::arg("dim"),
+            "(alpha_1..k, beta_2..k+1) of k <= dim Lanczos steps on H = sum of (coeff, [qubits], "
+            "[paulis]) terms from the current state, which is left bit-identical; k < dim is the "
+            "happy breakdown. No re-orthogonalisation")
+        .def("krylov_evolve_pauli_sum",
+            [](QI& q, std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms,
+                double time, int dim, int steps) {
+                return q.KrylovEvolvePauliSum(
+                    pauliTermsFromTuples(terms, "krylov_evolve_pauli_sum"), time, dim, steps);
+            },
+            py::arg("terms"), py::arg("time"), py::arg("dim") = 16, py::arg("steps") = 1,
+            "exp(-i time H) by Krylov projection onto `dim` Lanczos vectors per step; returns the "
+            "summed a-posteriori error estimates of the steps. The state may have any norm, which "
+            "it keeps. The dense engines need dim + 1 states of memory")
+        .def("lanczos_ground_state",
+            [](QI& q, std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms,
+                int dim, bool prepare) {
+                const std::pair<double, double> r
+                    = q.LanczosGroundState(pauliTermsFromTuples(terms, "lanczos_ground_state"), dim, prepare);
+                return py::make_tuple(r.first, r.second);
+            },
+            py::arg("terms"), py::arg("dim") = 32, py::arg("prepare") = false,
+            "(lowest Ritz value, its residual norm) of `dim` Lanczos steps from the current state; "
+            "prepare=True leaves the Ritz vector in the simulator at unit norm, so that calling "
+            "again is a restarted Lanczos")
         .def("prob_bits_all",
             [](QI& q, std::vector<bitLenInt> bits) {
                 py::array_t<double> out((py::ssize_t)pow2((bitLenInt)bits.size()));
@@ -1155,6 +1190,24 @@ PYBIND11_MODULE(_qrack, m)
         "contiguous run, the tiles visited, orbits per tile, rows per thread and where the matrix "
         "travels (\"kernarg\" | \"aux\"). check=True also walks every index the kernel would touch "
         "and reports under \"covers\" whether they are exactly the amplitudes to visit");
+    // host mathematics of the Krylov calls (krylov.hpp); needs no engine
+    m.def(
+        "krylov_coefficients",
+        [](std::vector<double> alpha, std::vector<double> beta, double time) {
+            if (alpha.empty()) throw std::invalid_argument("krylov_coefficients: alpha is empty");
+            if (beta.size() + 1u < alpha.size())
+                throw std::invalid_argument("krylov_coefficients: beta needs len(alpha) - 1 entries or more");
+            const std::vector<cplx<double>> c = krylovCoefficients(alpha, beta, time);
+            py::array_t<std::complex<double>> out((py::ssize_t)c.size());
+            for (size_t i = 0; i < c.size(); ++i) out.mutable_data()[i] = std::complex<double>(c[i].re, c[i].im);
+            return out;
+        },
+        py::arg("alpha"), py::arg("beta"), py::arg("time"),
+        "exp(-i time T) e_1 for the symmetric tridiagonal T with diagonal alpha and off-diagonal "
+        "beta[:len(alpha) - 1] (lanczos_tridiagonal's output can be passed as it is)");
+    m.attr("KRYLOV_MAX_DIM") = (int)KRYLOV_MAX_DIM;
+    // basis vectors one combine launch of the HIP engine adds to the state
+    m.attr("KRYLOV_COMBINE_MAX_VECTORS") = (int)KRYLOV_COMBINE_MAX_VECTORS;
     m.attr("MTRXN_MAX") = (int)QA_MTRXN_MAX;
     m.attr("RDM_MAX_QUBITS") = (int)QA_RDM_MAX_QUBITS;
     m.attr("RDM_REG_MAX") = (int)QA_RDM_REG_MAX;

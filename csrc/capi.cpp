@@ -696,6 +696,49 @@ void qrack_pauli_sum_apply_into(quid sid, uint64_t nTerms, const double* coeffs,
     });
 }
 
+uint64_t qrack_lanczos_tridiagonal(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, int dim, double* alpha, double* beta)
+{
+    uint64_t k = 0;
+    guarded(sid, [&](SimSlot& s) {
+        const std::vector<PauliTerm> terms
+            = flatPauliTerms(nTerms, coeffs, termLens, qs, paulis, "qrack_lanczos_tridiagonal");
+        std::vector<double> a, b;
+        FOR_SIM(s, q.LanczosTridiagonal(terms, dim, a, b));
+        std::copy(a.begin(), a.end(), alpha);
+        std::copy(b.begin(), b.end(), beta);
+        k = a.size();
+    });
+    return k;
+}
+
+double qrack_krylov_evolve_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, double time, int dim, int steps)
+{
+    return guardedD(sid, [&](SimSlot& s) -> double {
+        const std::vector<PauliTerm> terms
+            = flatPauliTerms(nTerms, coeffs, termLens, qs, paulis, "qrack_krylov_evolve_pauli_sum");
+        double e = 0;
+        FOR_SIM(s, e = q.KrylovEvolvePauliSum(terms, time, dim, steps));
+        return e;
+    });
+}
+
+double qrack_lanczos_ground_state(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, int dim, int prepare,
+    double* residual)
+{
+    *residual = 0;
+    return guardedD(sid, [&](SimSlot& s) -> double {
+        const std::vector<PauliTerm> terms
+            = flatPauliTerms(nTerms, coeffs, termLens, qs, paulis, "qrack_lanczos_ground_state");
+        std::pair<double, double> r(0, 0);
+        FOR_SIM(s, r = q.LanczosGroundState(terms, dim, prepare != 0));
+        *residual = r.second;
+        return r.first;
+    });
+}
+
 void qrack_qft(quid sid, uint64_t start, uint64_t length)
 {
     guarded(sid, [&](SimSlot& s) { FOR_SIM(s, q.QFT((bitLenInt)start, (bitLenInt)length)); });

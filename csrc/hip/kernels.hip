@@ -4315,6 +4315,340 @@ void launchPauliAdjoint(cplx<R>* psi, cplx<R>* lam, const PauliAdjointArgs& a, d
     launchPauliAdjointNt<R, false>(psi, lam, a, partialsDev, resultDev, stream);
 }
 
+// ---- Krylov: fused Lanczos step, basis combination ----------------------------------
+//
+// One Lanczos step (krylov.hpp) on the unnormalised basis is
+//   w = s H u - b prev,  A = Re <u|w>,  w <- w - s^2 A u,  ||w||^2
+// with s and b folded into the weight table, ident and bcoef by the host. The
+// apply kernels are k_pauli_apply with two additions: every pair adds its
+// share 2 Re(W conj(u[j]) u[i]) of A as a double partial (both amplitudes are
+// in registers already), and the FIRST form, which writes dest without reading
+// it, also takes - bcoef * prev from a third stream (prev == nullptr: none).
+// Each launch's block partials fold on the device into a slot of its own;
+// k_krylov_finish reads the slots back, so A never visits the host before w is
+// final. No atomics anywhere: every sum has a fixed order.
+
+// (re, im) of a - c p for one amplitude, and the share - c Re(conj(a) p) of A
+template <typename R>
+__device__ __forceinline__ void krylovPrev(R ar, R ai, R pr, R pi, R c, double cd, R& dr, R& di, double& s)
+{
+    dr -= c * pr;
+    di -= c * pi;
+    s -= cd * (double)(ar * pr + ai * pi);
+}
+
+template <typename R, int MODE, bool FIRST>
+__global__ void k_krylov_apply(const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, PauliArgs a,
+    double ident, double bcoef, bitCapInt nItems, bitCapInt topPow, double* partials)
+{
+    double s = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    const R id = (R)ident, bc = (R)bcoef;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        double wr0, wr1, wi0, wi1;
+        if constexpr (MODE == 0) {
+            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
+            const double2 A = reinterpret_cast<const double2*>(u)[i];
+            const double2 B = reinterpret_cast<const double2*>(u)[i ^ a.x];
+            double2* d = reinterpret_cast<double2*>(dest);
+            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            s += pauliPair<double>(A.x, A.y, B.x, B.y, wr0, wi0);
+            double2 DA, DB;
+            if constexpr (FIRST) {
+                DA = make_double2(id * A.x, id * A.y);
+                DB = make_double2(id * B.x, id * B.y);
+                s += ident * ((A.x * A.x + A.y * A.y) + (B.x * B.x + B.y * B.y));
+                if (prev) {
+                    const double2 P = reinterpret_cast<const double2*>(prev)[i];
+                    const double2 Q = reinterpret_cast<const double2*>(prev)[i ^ a.x];
+                    krylovPrev<double>(A.x, A.y, P.x, P.y, bc, bcoef, DA.x, DA.y, s);
+                    krylovPrev<double>(B.x, B.y, Q.x, Q.y, bc, bcoef, DB.x, DB.y, s);
+                }
+            } else {
+                DA = d[i];
+                DB = d[i ^ a.x];
+            }
+            pauliApplyMad<double>(wr0, -wi0, B.x, B.y, DA.x, DA.y);
+            pauliApplyMad<double>(wr0, wi0, A.x, A.y, DB.x, DB.y);
+            d[i] = DA;
+            d[i ^ a.x] = DB;
+        } else if constexpr (MODE == 1) {
+            const bitCapInt j = v << 1u;
+            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
+            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
+            const float4 A = reinterpret_cast<const float4*>(u)[ia];
+            float4 B = reinterpret_cast<const float4*>(u)[ib];
+            float4* d = reinterpret_cast<float4*>(dest);
+            const bool swapped = (a.x & 1u) != 0;
+            if (swapped) B = make_float4(B.z, B.w, B.x, B.y);
+            pauliWeights<true>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<true>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            s += pauliPair<float>(A.x, A.y, B.x, B.y, wr0, wi0);
+            s += pauliPair<float>(A.z, A.w, B.z, B.w, wr1, wi1);
+            float4 DA, DB;
+            if constexpr (FIRST) {
+                DA = make_float4(id * A.x, id * A.y, id * A.z, id * A.w);
+                DB = make_float4(id * B.x, id * B.y, id * B.z, id * B.w);
+                s += ident
+                    * (((double)(A.x * A.x + A.y * A.y) + (double)(A.z * A.z + A.w * A.w))
+                        + ((double)(B.x * B.x + B.y * B.y) + (double)(B.z * B.z + B.w * B.w)));
+                if (prev) {
+                    const float4 P = reinterpret_cast<const float4*>(prev)[ia];
+                    float4 Q = reinterpret_cast<const float4*>(prev)[ib];
+                    if (swapped) Q = make_float4(Q.z, Q.w, Q.x, Q.y);
+                    krylovPrev<float>(A.x, A.y, P.x, P.y, bc, bcoef, DA.x, DA.y, s);
+                    krylovPrev<float>(A.z, A.w, P.z, P.w, bc, bcoef, DA.z, DA.w, s);
+                    krylovPrev<float>(B.x, B.y, Q.x, Q.y, bc, bcoef, DB.x, DB.y, s);
+                    krylovPrev<float>(B.z, B.w, Q.z, Q.w, bc, bcoef, DB.z, DB.w, s);
+                }
+            } else {
+                DA = d[ia];
+                DB = d[ib];
+                if (swapped) DB = make_float4(DB.z, DB.w, DB.x, DB.y);
+            }
+            pauliApplyMad<float>((float)wr0, -(float)wi0, B.x, B.y, DA.x, DA.y);
+            pauliApplyMad<float>((float)wr1, -(float)wi1, B.z, B.w, DA.z, DA.w);
+            pauliApplyMad<float>((float)wr0, (float)wi0, A.x, A.y, DB.x, DB.y);
+            pauliApplyMad<float>((float)wr1, (float)wi1, A.z, A.w, DB.z, DB.w);
+            if (swapped) DB = make_float4(DB.z, DB.w, DB.x, DB.y);
+            d[ia] = DA;
+            d[ib] = DB;
+        } else {
+            const bitCapInt i = v << 1u;
+            const float4 A = reinterpret_cast<const float4*>(u)[v];
+            float4* d = reinterpret_cast<float4*>(dest);
+            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
+            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
+            s += pauliPair<float>(A.x, A.y, A.z, A.w, wr0, wi0);
+            float4 D;
+            if constexpr (FIRST) {
+                D = make_float4(id * A.x, id * A.y, id * A.z, id * A.w);
+                s += ident * ((double)(A.x * A.x + A.y * A.y) + (double)(A.z * A.z + A.w * A.w));
+                if (prev) {
+                    const float4 P = reinterpret_cast<const float4*>(prev)[v];
+                    krylovPrev<float>(A.x, A.y, P.x, P.y, bc, bcoef, D.x, D.y, s);
+                    krylovPrev<float>(A.z, A.w, P.z, P.w, bc, bcoef, D.z, D.w, s);
+                }
+            } else {
+                D = d[v];
+            }
+            pauliApplyMad<float>((float)wr0, -(float)wi0, A.z, A.w, D.x, D.y);
+            pauliApplyMad<float>((float)wr0, (float)wi0, A.x, A.y, D.z, D.w);
+            d[v] = D;
+        }
+    }
+    blockSumStore(s, partials + blockIdx.x);
+}
+
+// x == 0: dest[i] (+)= W(i) u[i], share W(i) |u[i]|^2; FIRST as above
+template <typename R, bool FIRST>
+__global__ void k_krylov_apply_diag(const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, PauliArgs a,
+    double ident, double bcoef, bitCapInt nItems, double* partials)
+{
+    double s = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    const R bc = (R)bcoef;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        double w0, w1;
+        if constexpr (sizeof(R) == 4) {
+            const float4 A = reinterpret_cast<const float4*>(u)[v];
+            float4* d = reinterpret_cast<float4*>(dest);
+            pauliWeights<true>(a, 0, a.nTerms, v << 1u, w0, w1);
+            if constexpr (FIRST) {
+                w0 += ident;
+                w1 += ident;
+            }
+            s += w0 * (double)(A.x * A.x + A.y * A.y) + w1 * (double)(A.z * A.z + A.w * A.w);
+            const float f0 = (float)w0, f1 = (float)w1;
+            float4 D;
+            if constexpr (FIRST) {
+                D = make_float4(f0 * A.x, f0 * A.y, f1 * A.z, f1 * A.w);
+                if (prev) {
+                    const float4 P = reinterpret_cast<const float4*>(prev)[v];
+                    krylovPrev<float>(A.x, A.y, P.x, P.y, bc, bcoef, D.x, D.y, s);
+                    krylovPrev<float>(A.z, A.w, P.z, P.w, bc, bcoef, D.z, D.w, s);
+                }
+            } else {
+                D = d[v];
+                D.x += f0 * A.x;
+                D.y += f0 * A.y;
+                D.z += f1 * A.z;
+                D.w += f1 * A.w;
+            }
+            d[v] = D;
+        } else {
+            const double2 A = reinterpret_cast<const double2*>(u)[v];
+            double2* d = reinterpret_cast<double2*>(dest);
+            pauliWeights<false>(a, 0, a.nTerms, v, w0, w1);
+            if constexpr (FIRST) w0 += ident;
+            s += w0 * (A.x * A.x + A.y * A.y);
+            double2 D;
+            if constexpr (FIRST) {
+                D = make_double2(w0 * A.x, w0 * A.y);
+                if (prev) {
+                    const double2 P = reinterpret_cast<const double2*>(prev)[v];
+                    krylovPrev<double>(A.x, A.y, P.x, P.y, bc, bcoef, D.x, D.y, s);
+                }
+            } else {
+                D = d[v];
+                D.x += w0 * A.x;
+                D.y += w0 * A.y;
+            }
+            d[v] = D;
+        }
+    }
+    blockSumStore(s, partials + blockIdx.x);
+}
+
+template <typename R, bool FIRST>
+static void launchKrylovApplyFirst(const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, const PauliArgs& a,
+    double ident, double bcoef, double* partialsDev, double* slotDev, hipStream_t stream)
+{
+    bitCapInt nItems, topPow;
+    const int mode = pauliPairMode<R>(a.x, a.nAmps, nItems, topPow);
+    const int grid = gridForPairs(nItems);
+    const dim3 g(grid), b(QA_BLOCK);
+    if (mode < 0) {
+        hipLaunchKernelGGL((k_krylov_apply_diag<R, FIRST>), g, b, 0, stream, u, prev, dest, a, ident, bcoef,
+            nItems, partialsDev);
+    } else if constexpr (sizeof(R) == 4) {
+        if (mode == 2) {
+            hipLaunchKernelGGL((k_krylov_apply<R, 2, FIRST>), g, b, 0, stream, u, prev, dest, a, ident, bcoef,
+                nItems, topPow, partialsDev);
+        } else {
+            hipLaunchKernelGGL((k_krylov_apply<R, 1, FIRST>), g, b, 0, stream, u, prev, dest, a, ident, bcoef,
+                nItems, topPow, partialsDev);
+        }
+    } else {
+        hipLaunchKernelGGL((k_krylov_apply<R, 0, FIRST>), g, b, 0, stream, u, prev, dest, a, ident, bcoef,
+            nItems, topPow, partialsDev);
+    }
+    hipLaunchKernelGGL(k_pauli_finish, dim3(1), dim3(QA_BLOCK), 0, stream, partialsDev, grid, slotDev);
+}
+
+template <typename R>
+void launchKrylovApply(const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, const PauliArgs& a, double ident,
+    double bcoef, bool first, double* partialsDev, double* slotDev, hipStream_t stream)
+{
+    if (first) {
+        launchKrylovApplyFirst<R, true>(u, prev, dest, a, ident, bcoef, partialsDev, slotDev, stream);
+    } else {
+        launchKrylovApplyFirst<R, false>(u, nullptr, dest, a, 0.0, 0.0, partialsDev, slotDev, stream);
+    }
+}
+
+// w <- w - a u with a = scale * (sum of the step's slots), and the block's
+// share of ||w||^2. STORE = false (the last step of a run) only sums.
+template <typename R, bool STORE>
+__global__ void k_krylov_finish(const cplx<R>* u, cplx<R>* w, const double* slots, int nSlots, double scale,
+    bitCapInt nItems, double* partials)
+{
+    double A = 0;
+    for (int k = 0; k < nSlots; ++k) A += slots[k];
+    const R a = (R)(scale * A);
+    double s = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        if constexpr (sizeof(R) == 4) {
+            const float4 U = reinterpret_cast<const float4*>(u)[v];
+            float4 W = reinterpret_cast<float4*>(w)[v];
+            W.x -= a * U.x;
+            W.y -= a * U.y;
+            W.z -= a * U.z;
+            W.w -= a * U.w;
+            if constexpr (STORE) reinterpret_cast<float4*>(w)[v] = W;
+            s += (double)(W.x * W.x + W.y * W.y) + (double)(W.z * W.z + W.w * W.w);
+        } else {
+            const double2 U = reinterpret_cast<const double2*>(u)[v];
+            double2 W = reinterpret_cast<double2*>(w)[v];
+            W.x -= a * U.x;
+            W.y -= a * U.y;
+            if constexpr (STORE) reinterpret_cast<double2*>(w)[v] = W;
+            s += W.x * W.x + W.y * W.y;
+        }
+    }
+    blockSumStore(s, partials + blockIdx.x);
+}
+
+// stage 2 of the finish: result[0] = sum of the slots, result[1] = ||w||^2
+__global__ void k_krylov_fold(const double* partials, int n, const double* slots, int nSlots, double* result)
+{
+    double s = 0;
+    for (int k = threadIdx.x; k < n; k += QA_BLOCK) s += partials[k];
+    blockSumStore(s, result + 1);
+    if (threadIdx.x == 0) {
+        double A = 0;
+        for (int k = 0; k < nSlots; ++k) A += slots[k];
+        result[0] = A;
+    }
+}
+
+template <typename R>
+void launchKrylovFinish(const cplx<R>* u, cplx<R>* w, bitCapInt nAmps, const double* slotsDev, int nSlots,
+    double scale, bool store, double* partialsDev, double* resultDev, hipStream_t stream)
+{
+    const bitCapInt nItems = (sizeof(R) == 4) ? (nAmps >> 1u) : nAmps;
+    const int grid = gridForPairs(nItems);
+    const dim3 g(grid), b(QA_BLOCK);
+    if (store) {
+        hipLaunchKernelGGL((k_krylov_finish<R, true>), g, b, 0, stream, u, w, slotsDev, nSlots, scale, nItems,
+            partialsDev);
+    } else {
+        hipLaunchKernelGGL((k_krylov_finish<R, false>), g, b, 0, stream, u, w, slotsDev, nSlots, scale, nItems,
+            partialsDev);
+    }
+    hipLaunchKernelGGL(
+        k_krylov_fold, dim3(1), dim3(QA_BLOCK), 0, stream, partialsDev, grid, slotsDev, nSlots, resultDev);
+}
+
+// (re, im) += (cr + i ci) (ur + i ui)
+template <typename R> __device__ __forceinline__ void krylovMad(R cr, R ci, R ur, R ui, R& re, R& im)
+{
+    re += cr * ur - ci * ui;
+    im += cr * ui + ci * ur;
+}
+
+// state <- coef[0] state + sum_j coef[j + 1] src[j]: elementwise, so in place
+// is safe. Pointers and coefficients ride in the kernel arguments.
+template <typename R>
+__global__ void k_krylov_combine(cplx<R>* state, KrylovCombineArgs<R> a, bitCapInt nItems)
+{
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        if constexpr (sizeof(R) == 4) {
+            const float4 S = reinterpret_cast<float4*>(state)[v];
+            float4 D = make_float4(0.f, 0.f, 0.f, 0.f);
+            krylovMad<float>((float)a.coefRe[0], (float)a.coefIm[0], S.x, S.y, D.x, D.y);
+            krylovMad<float>((float)a.coefRe[0], (float)a.coefIm[0], S.z, S.w, D.z, D.w);
+            for (int j = 0; j < a.nSrc; ++j) {
+                const float4 U = reinterpret_cast<const float4*>(a.src[j])[v];
+                const float cr = (float)a.coefRe[j + 1], ci = (float)a.coefIm[j + 1];
+                krylovMad<float>(cr, ci, U.x, U.y, D.x, D.y);
+                krylovMad<float>(cr, ci, U.z, U.w, D.z, D.w);
+            }
+            reinterpret_cast<float4*>(state)[v] = D;
+        } else {
+            const double2 S = reinterpret_cast<double2*>(state)[v];
+            double2 D = make_double2(0.0, 0.0);
+            krylovMad<double>(a.coefRe[0], a.coefIm[0], S.x, S.y, D.x, D.y);
+            for (int j = 0; j < a.nSrc; ++j) {
+                const double2 U = reinterpret_cast<const double2*>(a.src[j])[v];
+                krylovMad<double>(a.coefRe[j + 1], a.coefIm[j + 1], U.x, U.y, D.x, D.y);
+            }
+            reinterpret_cast<double2*>(state)[v] = D;
+        }
+    }
+}
+
+template <typename R>
+void launchKrylovCombine(cplx<R>* state, bitCapInt nAmps, const KrylovCombineArgs<R>& a, hipStream_t stream)
+{
+    const bitCapInt nItems = (sizeof(R) == 4) ? (nAmps >> 1u) : nAmps;
+    hipLaunchKernelGGL(
+        (k_krylov_combine<R>), dim3(gridForPairs(nItems)), dim3(QA_BLOCK), 0, stream, state, a, nItems);
+}
+
 // ---- reduced density matrices -----------------------------------------------------
 //
 // rho[a,b] = sum_e psi[e,a] conj(psi[e,b]) over the kept qubits in ascending
@@ -4668,6 +5002,12 @@ void launchRdmTile(const cplx<R>* sv, int kt, const RdmTileArgs& a, double* part
         const cplx<R>*, cplx<R>*, const PauliArgs&, double, bool, hipStream_t);                     \
     template void launchPauliAdjoint<R>(                                                            \
         cplx<R>*, cplx<R>*, const PauliAdjointArgs&, double*, double*, hipStream_t);                \
+    template void launchKrylovApply<R>(const cplx<R>*, const cplx<R>*, cplx<R>*, const PauliArgs&,  \
+        double, double, bool, double*, double*, hipStream_t);                                       \
+    template void launchKrylovFinish<R>(const cplx<R>*, cplx<R>*, bitCapInt, const double*, int,    \
+        double, bool, double*, double*, hipStream_t);                                               \
+    template void launchKrylovCombine<R>(                                                           \
+        cplx<R>*, bitCapInt, const KrylovCombineArgs<R>&, hipStream_t);                             \
     template void launchRdmReg<R>(                                                                  \
         const cplx<R>*, int, bool, const RdmRegArgs&, double*, double*, hipStream_t);               \
     template void launchRdmTile<R>(                                                                 \

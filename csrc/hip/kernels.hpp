@@ -10,6 +10,7 @@
 #pragma once
 
 #include "../common/types.hpp"
+#include "../krylov.hpp"
 #include "mtrxn_plan.hpp"
 #include "rdm_plan.hpp"
 
@@ -219,6 +220,37 @@ void launchPauliApply(const cplx<R>* psi, cplx<R>* dest, const PauliArgs& a, dou
 template <typename R>
 void launchPauliAdjoint(cplx<R>* psi, cplx<R>* lam, const PauliAdjointArgs& a, double* partialsDev,
     double* resultDev, hipStream_t stream);
+
+// One fused Lanczos step on the unnormalised basis (krylov.hpp): L apply
+// launches, then one finish. The weights of `a`, ident and bcoef arrive scaled
+// by the host. All three use the reduction grid under the QRACK_GPU_BLOCKS cap.
+//
+// dest = (ident + sum_t w_t P_t) u - bcoef prev when `first` (dest is not read;
+// prev may be null: no such term), else dest += (sum_t w_t P_t) u. *slotDev
+// takes the launch's share of Re <u|dest>, block partials (QA_REDUCE_MAX_BLOCKS
+// doubles in partialsDev) folded on the device. dest aliases neither input.
+template <typename R>
+void launchKrylovApply(const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, const PauliArgs& a, double ident,
+    double bcoef, bool first, double* partialsDev, double* slotDev, hipStream_t stream);
+
+// w <- w - a u with a = scale * (slotsDev[0] + ... + slotsDev[nSlots - 1]),
+// read on the device; resultDev <- (sum of the slots, ||w||^2). With !store w
+// is left as it was and only the norm is formed.
+template <typename R>
+void launchKrylovFinish(const cplx<R>* u, cplx<R>* w, bitCapInt nAmps, const double* slotsDev, int nSlots,
+    double scale, bool store, double* partialsDev, double* resultDev, hipStream_t stream);
+
+// state <- coef[0] state + sum_j coef[j + 1] src[j], complex coefficients
+// formed in double by the host, for up to KRYLOV_COMBINE_MAX_VECTORS sources
+template <typename R> struct KrylovCombineArgs {
+    const cplx<R>* src[KRYLOV_COMBINE_MAX_VECTORS];
+    double coefRe[KRYLOV_COMBINE_MAX_VECTORS + 1];
+    double coefIm[KRYLOV_COMBINE_MAX_VECTORS + 1];
+    int nSrc;
+};
+
+template <typename R>
+void launchKrylovCombine(cplx<R>* state, bitCapInt nAmps, const KrylovCombineArgs<R>& a, hipStream_t stream);
 
 template <typename R>
 void launchApply2x2(cplx<R>* sv, const GateArgs<R>& a, hipStream_t stream);

@@ -1832,6 +1832,143 @@ double QEngineHIP<R>::AdjointGradient(const std::vector<AdjointOp<R>>& ops,
     return hRes[0];
 }
 
+// ---- Krylov evolution and Lanczos (krylov.hpp) ---------------------------------
+
+static_assert((size_t)QA_PAULI_MAX_TERMS == PAULI_SUM_LAUNCH_TERMS,
+    "pauliSumLaunchCount's default chunk is the launch table's size");
+
+template <typename R>
+KrylovRun QEngineHIP<R>::lanczosRun(
+    const PauliCanonSum& c, int dim, const std::vector<cplx<R>*>& bufs, const char* what)
+{
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    const std::vector<PauliArgs> launches = pauliSumLaunches(c, maxQPower);
+    const size_t L = launches.size();
+    ReduceArgs ra{};
+    ra.maxI = maxQPower;
+    const double nrm = reduceSum((int)ReduceOp::NORM_ALL, ra);
+    if (!(nrm > 0)) throw QrackError(std::string(what) + ": the state has zero norm");
+    const double theta = krylovTheta(L, (double)std::numeric_limits<R>::epsilon(), pauliSumAbsWeights(c));
+    // one slot per launch for its share of alpha, then (alpha's sum, beta^2)
+    double* dSlots = pairResults((L + 3u) / 2u);
+    double* dRes = dSlots + L;
+    const cplx<R>* sv = rState();
+    const size_t nb = bufs.size();
+    return lanczosDrive(dim, std::sqrt(nrm), theta, [&](int j, double s, double b) {
+        const cplx<R>* u = (j == 1) ? sv : bufs[(size_t)(j - 2) % nb];
+        const cplx<R>* prev = (j == 1) ? nullptr : (j == 2) ? sv : bufs[(size_t)(j - 3) % nb];
+        cplx<R>* dest = bufs[(size_t)(j - 1) % nb];
+        for (size_t k = 0; k < L; ++k) {
+            // the scale of the unnormalised basis rides in the weights, in double
+            PauliArgs a = launches[k];
+            for (int t = 0; t < a.nTerms; ++t) a.w[t] *= s;
+            HipProfScope prof("krylov_apply", stream);
+            launchKrylovApply<R>(u, prev, dest, a, s * c.identity, b, k == 0u, dPartials, dSlots + k, stream);
+        }
+        double h[2] = { 0, 0 };
+        {
+            HipProfScope prof("krylov_finish", stream);
+            launchKrylovFinish<R>(u, dest, maxQPower, dSlots, (int)L, s * s, j < dim, dPartials, dRes, stream);
+            QA_HIP_CHECK(hipMemcpyAsync(h, dRes, sizeof(h), hipMemcpyDeviceToHost, stream));
+            Finish(); // the host needs beta for the next scale
+        }
+        return std::pair<double, double>(h[0], h[1]);
+    });
+}
+
+template <typename R>
+void QEngineHIP<R>::krylovCombine(const std::vector<cplx<double>>& coef, const std::vector<cplx<R>*>& bufs)
+{
+    cplx<R>* sv = wState();
+    const size_t nSrc = coef.size() - 1u;
+    size_t done = 0;
+    bool first = true;
+    do {
+        KrylovCombineArgs<R> a{};
+        a.coefRe[0] = first ? coef[0].re : 1.0;
+        a.coefIm[0] = first ? coef[0].im : 0.0;
+        while (a.nSrc < KRYLOV_COMBINE_MAX_VECTORS && done < nSrc) {
+            a.src[a.nSrc] = bufs[done];
+            a.coefRe[a.nSrc + 1] = coef[done + 1u].re;
+            a.coefIm[a.nSrc + 1] = coef[done + 1u].im;
+            ++a.nSrc;
+            ++done;
+        }
+        HipProfScope prof("krylov_combine", stream);
+        launchKrylovCombine<R>(sv, maxQPower, a, stream);
+        first = false;
+    } while (done < nSrc);
+    Finish(); // the sources are freed by the caller
+}
+
+template <typename R>
+void QEngineHIP<R>::LanczosTridiagonal(const std::vector<PauliTerm>& terms, int dim,
+    std::vector<double>& alpha, std::vector<double>& beta)
+{
+    validateKrylovArgs(dim, 1, "LanczosTridiagonal");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "LanczosTridiagonal");
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    KrylovBuffers bufs(this);
+    bufs.take((size_t)std::min(dim, 3));
+    const KrylovRun run = lanczosRun(c, dim, bufs.p, "LanczosTridiagonal");
+    alpha = run.alpha;
+    beta = run.beta;
+}
+
+template <typename R>
+double QEngineHIP<R>::KrylovEvolvePauliSum(const std::vector<PauliTerm>& terms, double time, int dim, int steps)
+{
+    validateKrylovArgs(dim, steps, "KrylovEvolvePauliSum");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "KrylovEvolvePauliSum");
+    if (time == 0) return 0.0;
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    KrylovBuffers bufs(this);
+    bufs.take((size_t)dim);
+    const double tau = time / steps;
+    double estimate = 0;
+    for (int st = 0; st < steps; ++st) {
+        const KrylovRun run = lanczosRun(c, dim, bufs.p, "KrylovEvolvePauliSum");
+        std::vector<cplx<double>> coef = krylovCoefficients(run.alpha, run.beta, tau);
+        const size_t k = run.k();
+        estimate += run.beta[k - 1u]
+            * std::sqrt(coef[k - 1u].re * coef[k - 1u].re + coef[k - 1u].im * coef[k - 1u].im);
+        for (size_t j = 0; j < k; ++j) coef[j] = (run.norm0 * run.scale[j]) * coef[j];
+        krylovCombine(coef, bufs.p);
+        runningNorm = (R)-1;
+    }
+    return estimate;
+}
+
+template <typename R>
+std::pair<double, double> QEngineHIP<R>::LanczosGroundState(const std::vector<PauliTerm>& terms, int dim, bool prepare)
+{
+    validateKrylovArgs(dim, 1, "LanczosGroundState");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "LanczosGroundState");
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    KrylovBuffers bufs(this);
+    bufs.take((size_t)(prepare ? dim : std::min(dim, 3)));
+    const KrylovRun run = lanczosRun(c, dim, bufs.p, "LanczosGroundState");
+    std::vector<double> y;
+    const double lambda = krylovLowestRitz(run.alpha, run.beta, y);
+    const size_t k = run.k();
+    if (prepare) {
+        std::vector<cplx<double>> coef(k);
+        for (size_t j = 0; j < k; ++j) coef[j] = cplx<double>(y[j] * run.scale[j], 0.0);
+        krylovCombine(coef, bufs.p);
+        // without re-orthogonalisation the basis is orthonormal only until a
+        // Ritz pair converges, and the sum's norm is off by as much: one
+        // reduction and one scaling pass make "unit norm" hold
+        ReduceArgs ra{};
+        ra.maxI = maxQPower;
+        const double nrm = reduceSum((int)ReduceOp::NORM_ALL, ra);
+        if (nrm > 0) {
+            launchNormalize<R>(wState(), maxQPower, cplx<R>((R)(1.0 / std::sqrt(nrm)), (R)0), (R)0, stream);
+        }
+        runningNorm = (R)1;
+    }
+    return { lambda, run.beta[k - 1u] * std::abs(y[k - 1u]) };
+}
+
 template <typename R> std::pair<double, bitCapInt> QEngineHIP<R>::argMax()
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));

@@ -238,6 +238,19 @@ public:
     // the stream.)
     double AdjointGradient(const std::vector<AdjointOp<R>>& ops, const std::vector<PauliTerm>& terms,
         std::vector<double>& grad) override;
+    // Krylov calls (krylov.hpp), all through lanczosRun. A Lanczos step is L
+    // fused apply launches and one finish, (3L + 3) state sizes of traffic,
+    // and one host sync that brings (alpha, beta^2) back for the next scale;
+    // the basis stays unnormalised and no pass exists only to scale. The
+    // tridiagonal rotates three buffers (peak: 4 states); the evolution and
+    // the preparing ground state keep u_2..u_dim and a work buffer (peak:
+    // dim + 1 states), taken up front so that a refusal leaves the state alone.
+    void LanczosTridiagonal(const std::vector<PauliTerm>& terms, int dim, std::vector<double>& alpha,
+        std::vector<double>& beta) override;
+    double KrylovEvolvePauliSum(
+        const std::vector<PauliTerm>& terms, double time, int dim = 16, int steps = 1) override;
+    std::pair<double, double> LanczosGroundState(
+        const std::vector<PauliTerm>& terms, int dim = 32, bool prepare = false) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;
@@ -305,6 +318,31 @@ protected:
     // exp(-i angle P) for the one string of g on a raw buffer (a state or the
     // adjoint sweep's second vector), through the evolution launcher
     void pauliRotateBuffer(cplx<R>* buf, const PauliGroup& g, double angle);
+    // raw accounted state-sized buffers of one Krylov call, freed on every way out
+    struct KrylovBuffers {
+        QEngineHIP<R>* self;
+        std::vector<cplx<R>*> p;
+        explicit KrylovBuffers(QEngineHIP<R>* s)
+            : self(s)
+        {
+        }
+        KrylovBuffers(const KrylovBuffers&) = delete;
+        KrylovBuffers& operator=(const KrylovBuffers&) = delete;
+        ~KrylovBuffers()
+        {
+            for (cplx<R>* q : p) self->freeDev(q, self->maxQPower);
+        }
+        void take(size_t n)
+        {
+            p.reserve(n);
+            while (p.size() < n) p.push_back(self->allocDev(self->maxQPower));
+        }
+    };
+    // Lanczos(dim) from the state: step j writes bufs[(j - 1) % bufs.size()]
+    KrylovRun lanczosRun(const PauliCanonSum& c, int dim, const std::vector<cplx<R>*>& bufs, const char* what);
+    // state <- coef[0] state + sum_j coef[j] bufs[j - 1], in as many launches
+    // as KRYLOV_COMBINE_MAX_VECTORS sources each take
+    void krylovCombine(const std::vector<cplx<double>>& coef, const std::vector<cplx<R>*>& bufs);
     // device slots for `n` (re, im) results of the pair-walk reductions
     double* pairResults(size_t n);
     void releasePairResults();

@@ -11,9 +11,11 @@
 // antidiagonal (invert) matrices internally.
 #pragma once
 
+#include "krylov.hpp"
 #include "qinterface.hpp"
 
 #include <algorithm>
+#include <cmath>
 
 namespace qrack_amd {
 
@@ -102,6 +104,30 @@ inline PauliCanonSum canonicalizePauliSum(const std::vector<PauliTerm>& terms, b
         pauliGroupAdd(out.groups.back(), z, kv.second);
     }
     return out;
+}
+
+// L and S of the Krylov calls (krylov.hpp): the launches of one pass over a
+// canonical sum on the HIP engine, one per (group, chunk of `cap` terms) and
+// one for identities alone, and |identity| plus the summed |weight|.
+// PAULI_SUM_LAUNCH_TERMS is the HIP launch table's size: the HIP engine
+// asserts that it equals QA_PAULI_MAX_TERMS, so that every engine uses one L.
+constexpr size_t PAULI_SUM_LAUNCH_TERMS = 32;
+
+inline size_t pauliSumLaunchCount(const PauliCanonSum& c, size_t cap = PAULI_SUM_LAUNCH_TERMS)
+{
+    size_t n = 0;
+    for (const PauliGroup& g : c.groups) n += (g.re.size() + g.im.size() + cap - 1u) / cap;
+    return n ? n : 1u;
+}
+
+inline double pauliSumAbsWeights(const PauliCanonSum& c)
+{
+    double s = std::abs(c.identity);
+    for (const PauliGroup& g : c.groups) {
+        for (const PauliCanonTerm& t : g.re) s += std::abs(t.w);
+        for (const PauliCanonTerm& t : g.im) s += std::abs(t.w);
+    }
+    return s;
 }
 
 // ---- Pauli-sum evolution plan (shared by the dense engines) -----------------

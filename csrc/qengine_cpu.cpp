@@ -1088,6 +1088,221 @@ double QEngineCPU<R>::AdjointGradient(const std::vector<AdjointOp<R>>& ops,
     return energy;
 }
 
+// ---- Krylov evolution and Lanczos (krylov.hpp) ---------------------------------
+
+namespace {
+// A worker's slice is summed serially, and a plain sum of 2^n like terms (a
+// uniform superposition) drifts by n-dependent many eps, which beta and the
+// next scale would inherit. par_sum2's second sum carries Kahan's
+// compensation instead: the total is (sum of the sums) - (sum of the terms).
+inline void kahanAdd(double& sum, double& comp, double x)
+{
+    const double y = x - comp;
+    const double t = sum + y;
+    comp = (t - sum) - y;
+    sum = t;
+}
+} // namespace
+
+template <typename R>
+std::pair<double, double> QEngineCPU<R>::krylovStep(const PauliCanonSum& c, double s, double b,
+    const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, bool store)
+{
+    // the sweeps of pauliApplyRun with the weights scaled by s; the first one
+    // also takes - b prev, and each adds its pairs' share of A
+    double A = 0;
+    bool first = true;
+    const R bc = (R)b;
+    auto sweep = [&](const PauliGroup& g) {
+        const PauliCanonTerm* re = g.re.data();
+        const PauliCanonTerm* im = g.im.data();
+        const size_t nRe = g.re.size(), nIm = g.im.size();
+        const bool isFirst = first;
+        const double id = s * c.identity;
+        first = false;
+        double part = 0, comp = 0;
+        if (!g.x) {
+            this->par_sum2(maxQPower, [=](const bitCapInt& i, double& sum, double& cmp) {
+                double acc = 0;
+                double wr, wi;
+                pauliGroupWeights(re, nRe, im, 0, i, wr, wi);
+                wr *= s;
+                const cplx<R> a = u[i];
+                const double aa = (double)(a.re * a.re + a.im * a.im);
+                if (isFirst) {
+                    cplx<R> d = (R)(wr + id) * a;
+                    acc += (wr + id) * aa;
+                    if (prev) {
+                        const cplx<R> p = prev[i];
+                        d = d - bc * p;
+                        acc -= b * (double)(a.re * p.re + a.im * p.im);
+                    }
+                    dest[i] = d;
+                } else {
+                    dest[i] = dest[i] + (R)wr * a;
+                    acc += wr * aa;
+                }
+                kahanAdd(sum, cmp, acc);
+            }, part, comp);
+            A += part - comp;
+            return;
+        }
+        const bitCapInt x = g.x;
+        const bitCapInt topPow = pow2(log2Ocl(x));
+        this->par_sum2(maxQPower >> 1u, [=](const bitCapInt& j, double& sum, double& cmp) {
+            double acc = 0;
+            const bitCapInt i = insertZeroBit(j, topPow);
+            double wr, wi;
+            pauliGroupWeights(re, nRe, im, nIm, i, wr, wi);
+            wr *= s;
+            wi *= s;
+            const cplx<R> a = u[i], q = u[i ^ x];
+            const cplx<R> w((R)wr, (R)wi);
+            // 2 Re (W conj(q) a): the pair's share of <u|(sum_t w_t P_t)|u>
+            const R pr = q.re * a.re + q.im * a.im, pi = q.re * a.im - q.im * a.re;
+            acc += 2.0 * (wr * (double)pr - wi * (double)pi);
+            cplx<R> da, db;
+            if (isFirst) {
+                da = (R)id * a;
+                db = (R)id * q;
+                acc += id * ((double)(a.re * a.re + a.im * a.im) + (double)(q.re * q.re + q.im * q.im));
+                if (prev) {
+                    const cplx<R> p = prev[i], pq = prev[i ^ x];
+                    da = da - bc * p;
+                    db = db - bc * pq;
+                    acc -= b * ((double)(a.re * p.re + a.im * p.im) + (double)(q.re * pq.re + q.im * pq.im));
+                }
+            } else {
+                da = dest[i];
+                db = dest[i ^ x];
+            }
+            dest[i] = da + conj(w) * q;
+            dest[i ^ x] = db + w * a;
+            kahanAdd(sum, cmp, acc);
+        }, part, comp);
+        A += part - comp;
+    };
+    for (const PauliGroup& g : c.groups) sweep(g);
+    if (first) sweep(PauliGroup{});
+    // the finishing sweep: w <- w - a u, and ||w||^2
+    const R a = (R)(s * s * A);
+    double nrm = 0, comp = 0;
+    this->par_sum2(maxQPower, [=](const bitCapInt& i, double& sum, double& cmp) {
+        const cplx<R> w = dest[i] - a * u[i];
+        if (store) dest[i] = w;
+        kahanAdd(sum, cmp, (double)(w.re * w.re + w.im * w.im));
+    }, nrm, comp);
+    return { A, nrm - comp };
+}
+
+template <typename R>
+KrylovRun QEngineCPU<R>::lanczosRun(
+    const PauliCanonSum& c, int dim, std::vector<std::vector<cplx<R>>>& bufs, const char* what)
+{
+    const cplx<R>* sv = stateVec.data();
+    double nrm = 0, comp = 0;
+    this->par_sum2(maxQPower, [=](const bitCapInt& i, double& sum, double& cmp) {
+        kahanAdd(sum, cmp, (double)(sv[i].re * sv[i].re + sv[i].im * sv[i].im));
+    }, nrm, comp);
+    nrm -= comp;
+    if (!(nrm > 0)) throw QrackError(std::string(what) + ": the state has zero norm");
+    const double theta = krylovTheta(
+        pauliSumLaunchCount(c), (double)std::numeric_limits<R>::epsilon(), pauliSumAbsWeights(c));
+    const size_t nb = bufs.size();
+    return lanczosDrive(dim, std::sqrt(nrm), theta, [&](int j, double s, double b) {
+        const cplx<R>* u = (j == 1) ? sv : bufs[(size_t)(j - 2) % nb].data();
+        const cplx<R>* prev = (j == 1) ? nullptr : (j == 2) ? sv : bufs[(size_t)(j - 3) % nb].data();
+        return krylovStep(c, s, b, u, prev, bufs[(size_t)(j - 1) % nb].data(), j < dim);
+    });
+}
+
+template <typename R>
+void QEngineCPU<R>::krylovCombine(
+    const std::vector<cplx<double>>& coef, const std::vector<std::vector<cplx<R>>>& bufs)
+{
+    std::vector<cplx<R>> cf;
+    std::vector<const cplx<R>*> src;
+    for (size_t j = 0; j < coef.size(); ++j) {
+        cf.push_back(cplx<R>((R)coef[j].re, (R)coef[j].im));
+        if (j) src.push_back(bufs[j - 1u].data());
+    }
+    cplx<R>* sv = stateVec.data();
+    const cplx<R>* cfp = cf.data();
+    const cplx<R>* const* srcp = src.data();
+    const size_t n = src.size();
+    this->par_for(0, maxQPower, [=](const bitCapInt& i, unsigned) {
+        cplx<R> acc = cfp[0] * sv[i];
+        for (size_t j = 0; j < n; ++j) acc = acc + cfp[j + 1u] * srcp[j][i];
+        sv[i] = acc;
+    });
+}
+
+template <typename R>
+void QEngineCPU<R>::LanczosTridiagonal(const std::vector<PauliTerm>& terms, int dim,
+    std::vector<double>& alpha, std::vector<double>& beta)
+{
+    validateKrylovArgs(dim, 1, "LanczosTridiagonal");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "LanczosTridiagonal");
+    std::vector<std::vector<cplx<R>>> bufs((size_t)std::min(dim, 3), std::vector<cplx<R>>(maxQPower));
+    const KrylovRun run = lanczosRun(c, dim, bufs, "LanczosTridiagonal");
+    alpha = run.alpha;
+    beta = run.beta;
+}
+
+template <typename R>
+double QEngineCPU<R>::KrylovEvolvePauliSum(const std::vector<PauliTerm>& terms, double time, int dim, int steps)
+{
+    validateKrylovArgs(dim, steps, "KrylovEvolvePauliSum");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "KrylovEvolvePauliSum");
+    if (time == 0) return 0.0;
+    std::vector<std::vector<cplx<R>>> bufs((size_t)dim, std::vector<cplx<R>>(maxQPower));
+    const double tau = time / steps;
+    double estimate = 0;
+    for (int st = 0; st < steps; ++st) {
+        const KrylovRun run = lanczosRun(c, dim, bufs, "KrylovEvolvePauliSum");
+        std::vector<cplx<double>> coef = krylovCoefficients(run.alpha, run.beta, tau);
+        const size_t k = run.k();
+        estimate += run.beta[k - 1u] * std::sqrt(coef[k - 1u].re * coef[k - 1u].re + coef[k - 1u].im * coef[k - 1u].im);
+        for (size_t j = 0; j < k; ++j) coef[j] = (run.norm0 * run.scale[j]) * coef[j];
+        krylovCombine(coef, bufs);
+        runningNorm = (R)-1;
+    }
+    return estimate;
+}
+
+template <typename R>
+std::pair<double, double> QEngineCPU<R>::LanczosGroundState(const std::vector<PauliTerm>& terms, int dim, bool prepare)
+{
+    validateKrylovArgs(dim, 1, "LanczosGroundState");
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "LanczosGroundState");
+    std::vector<std::vector<cplx<R>>> bufs(
+        (size_t)(prepare ? dim : std::min(dim, 3)), std::vector<cplx<R>>(maxQPower));
+    const KrylovRun run = lanczosRun(c, dim, bufs, "LanczosGroundState");
+    std::vector<double> y;
+    const double lambda = krylovLowestRitz(run.alpha, run.beta, y);
+    const size_t k = run.k();
+    if (prepare) {
+        std::vector<cplx<double>> coef(k);
+        for (size_t j = 0; j < k; ++j) coef[j] = cplx<double>(y[j] * run.scale[j], 0.0);
+        krylovCombine(coef, bufs);
+        // without re-orthogonalisation the basis is orthonormal only until a
+        // Ritz pair converges, and the sum's norm is off by as much: one
+        // reduction and one scaling pass make "unit norm" hold
+        cplx<R>* sv = stateVec.data();
+        double nrm = 0, comp = 0;
+        this->par_sum2(maxQPower, [=](const bitCapInt& i, double& sum, double& cmp) {
+            kahanAdd(sum, cmp, (double)(sv[i].re * sv[i].re + sv[i].im * sv[i].im));
+        }, nrm, comp);
+        nrm -= comp;
+        if (nrm > 0) {
+            const R f = (R)(1.0 / std::sqrt(nrm));
+            this->par_for(0, maxQPower, [=](const bitCapInt& i, unsigned) { sv[i] = f * sv[i]; });
+        }
+        runningNorm = (R)1;
+    }
+    return { lambda, run.beta[k - 1u] * std::abs(y[k - 1u]) };
+}
+
 template <typename R> bool QEngineCPU<R>::ForceMParity(bitCapInt mask, bool result, bool doForce)
 {
     if (!mask) return false;

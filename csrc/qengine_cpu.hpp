@@ -116,6 +116,16 @@ public:
     void PauliSumApplyInto(const std::vector<PauliTerm>& terms, QInterfacePtr<R> dest) override;
     double AdjointGradient(const std::vector<AdjointOp<R>>& ops, const std::vector<PauliTerm>& terms,
         std::vector<double>& grad) override;
+    // Krylov calls (krylov.hpp): a Lanczos step is one sweep per X/Y mask that
+    // also sums alpha's share, and one finishing sweep that returns beta^2;
+    // sums are private per worker and added in worker order. The two calls
+    // that need the basis keep dim amplitude arrays, the tridiagonal three.
+    void LanczosTridiagonal(const std::vector<PauliTerm>& terms, int dim, std::vector<double>& alpha,
+        std::vector<double>& beta) override;
+    double KrylovEvolvePauliSum(
+        const std::vector<PauliTerm>& terms, double time, int dim = 16, int steps = 1) override;
+    std::pair<double, double> LanczosGroundState(
+        const std::vector<PauliTerm>& terms, int dim = 32, bool prepare = false) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;
@@ -186,6 +196,16 @@ protected:
     void pauliApplyRun(const PauliCanonSum& c, const cplx<R>* psi, cplx<R>* dest);
     // <lam|P|psi> for the one string of g, then exp(-i angle P) on both arrays
     cplx<double> pauliAdjointStep(const PauliGroup& g, double angle, cplx<R>* psi, cplx<R>* lam);
+    // dest <- s H u - b prev - a u with a = s^2 A, A = Re <u | s H u - b prev>
+    // (prev may be null when b == 0; dest keeps s H u - b prev when !store);
+    // returns (A, ||s H u - b prev - a u||^2)
+    std::pair<double, double> krylovStep(const PauliCanonSum& c, double s, double b, const cplx<R>* u,
+        const cplx<R>* prev, cplx<R>* dest, bool store);
+    // Lanczos(dim) from the state: step j writes bufs[(j - 1) % bufs.size()]
+    KrylovRun lanczosRun(const PauliCanonSum& c, int dim, std::vector<std::vector<cplx<R>>>& bufs,
+        const char* what);
+    // state <- coef[0] state + sum_j coef[j] bufs[j - 1]
+    void krylovCombine(const std::vector<cplx<double>>& coef, const std::vector<std::vector<cplx<R>>>& bufs);
     bool pauliStringNative(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis,
         const char* what, double& value);
 

@@ -234,6 +234,24 @@ public:
         FlushAll();
         return inner->AdjointGradient(ops, t, grad);
     }
+    void LanczosTridiagonal(const std::vector<PauliTerm>& t, int dim, std::vector<double>& alpha,
+        std::vector<double>& beta) override
+    {
+        FlushAll();
+        inner->LanczosTridiagonal(t, dim, alpha, beta);
+    }
+    double KrylovEvolvePauliSum(
+        const std::vector<PauliTerm>& t, double time, int dim = 16, int steps = 1) override
+    {
+        FlushAll();
+        return inner->KrylovEvolvePauliSum(t, time, dim, steps);
+    }
+    std::pair<double, double> LanczosGroundState(
+        const std::vector<PauliTerm>& t, int dim = 32, bool prepare = false) override
+    {
+        FlushAll();
+        return inner->LanczosGroundState(t, dim, prepare);
+    }
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override { FlushAll(); return inner->TrySeparate(q); }

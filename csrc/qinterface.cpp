@@ -844,6 +844,56 @@ double QInterface<R>::AdjointGradient(const std::vector<AdjointOp<R>>& ops,
     return engine->AdjointGradient(ops, terms, grad);
 }
 
+// ---- Krylov calls: the CPU engine's run on a copy -----------------------------
+
+template <typename R>
+static std::shared_ptr<QEngineCPU<R>> krylovHostEngine(QInterface<R>& q, const std::vector<PauliTerm>& terms,
+    int dim, int steps, const char* what)
+{
+    validateKrylovArgs(dim, steps, what);
+    validatePauliTerms(terms, q.GetQubitCount(), what);
+    if (q.GetQubitCount() > 26u) throw QrackError(std::string(what) + ": dense fallback width cap");
+    std::vector<cplx<R>> sv(q.GetMaxQPower());
+    q.GetQuantumState(sv.data());
+    auto engine = std::make_shared<QEngineCPU<R>>(q.GetQubitCount(), 0u, nullptr, false);
+    engine->SetQuantumState(sv.data());
+    return engine;
+}
+
+template <typename R> static void krylovCopyBack(QInterface<R>& q, QEngineCPU<R>& engine)
+{
+    std::vector<cplx<R>> sv(q.GetMaxQPower());
+    engine.GetQuantumState(sv.data());
+    q.SetQuantumState(sv.data());
+}
+
+template <typename R>
+void QInterface<R>::LanczosTridiagonal(const std::vector<PauliTerm>& terms, int dim,
+    std::vector<double>& alpha, std::vector<double>& beta)
+{
+    krylovHostEngine(*this, terms, dim, 1, "LanczosTridiagonal")->LanczosTridiagonal(terms, dim, alpha, beta);
+}
+
+template <typename R>
+double QInterface<R>::KrylovEvolvePauliSum(const std::vector<PauliTerm>& terms, double time, int dim, int steps)
+{
+    auto engine = krylovHostEngine(*this, terms, dim, steps, "KrylovEvolvePauliSum");
+    if (time == 0) return 0.0;
+    const double est = engine->KrylovEvolvePauliSum(terms, time, dim, steps);
+    krylovCopyBack(*this, *engine);
+    return est;
+}
+
+template <typename R>
+std::pair<double, double> QInterface<R>::LanczosGroundState(
+    const std::vector<PauliTerm>& terms, int dim, bool prepare)
+{
+    auto engine = krylovHostEngine(*this, terms, dim, 1, "LanczosGroundState");
+    const std::pair<double, double> r = engine->LanczosGroundState(terms, dim, prepare);
+    if (prepare) krylovCopyBack(*this, *engine);
+    return r;
+}
+
 // ---- ALU defaults ----------------------------------------------------------
 
 template <typename R> static void aluThrow()

@@ -12,6 +12,7 @@
 
 #include "common/rng.hpp"
 #include "common/types.hpp"
+#include "krylov.hpp"
 
 #include <algorithm>
 #include <map>
@@ -45,6 +46,15 @@ inline void validatePauliTerms(const std::vector<PauliTerm>& terms, bitLenInt qu
             }
         }
     }
+}
+
+// Argument check of the three Krylov calls, shared by every implementation
+inline void validateKrylovArgs(int dim, int steps, const char* what)
+{
+    if (dim < 1 || dim > KRYLOV_MAX_DIM) {
+        throw QrackError(std::string(what) + ": need 1 <= dim <= " + std::to_string(KRYLOV_MAX_DIM));
+    }
+    if (steps < 1) throw QrackError(std::string(what) + ": steps must be at least 1");
 }
 
 // most qubits a reduced density matrix may keep (a 4096 x 4096 result)
@@ -944,6 +954,34 @@ public:
     // call; the simulator itself is untouched.
     virtual double AdjointGradient(const std::vector<AdjointOp<R>>& ops,
         const std::vector<PauliTerm>& terms, std::vector<double>& grad);
+    // The three Krylov calls share one Lanczos run on H = sum_t coeff_t P_t
+    // from the current state (krylov.hpp has the definition and the host
+    // mathematics): k <= dim steps, stopped early by the happy breakdown
+    // beta_(k+1) <= theta. There is no re-orthogonalisation. All three throw
+    // QrackError unless 1 <= dim <= KRYLOV_MAX_DIM, on a state of zero norm
+    // and on what EvolvePauliSum throws on. Default lowering: the state is
+    // copied into a CPU engine of the same width (at most 26 qubits), which
+    // runs the call; the two mutating forms copy the result back.
+    //
+    // alpha <- alpha_1..k and beta <- beta_2..(k+1) of the tridiagonal
+    // projection T_k; the state is left bit-identical.
+    virtual void LanczosTridiagonal(const std::vector<PauliTerm>& terms, int dim,
+        std::vector<double>& alpha, std::vector<double>& beta);
+    // exp(-i time H) by Krylov projection: every one of `steps` (>= 1) steps
+    // of tau = time / steps runs Lanczos(dim) from the current state and
+    // replaces it by ||psi|| sum_j c_j v_j with c = exp(-i tau T_k) e_1. The
+    // input may have any norm, which the output keeps. Returns the summed
+    // a-posteriori estimates beta_(k+1) |c_k| of the steps. time == 0 returns
+    // 0 and touches nothing; negative time is allowed. Needs dim + 1 states
+    // of memory on the dense engines.
+    virtual double KrylovEvolvePauliSum(
+        const std::vector<PauliTerm>& terms, double time, int dim = 16, int steps = 1);
+    // (lambda, beta_(k+1) |y_k|) for the lowest eigenpair (lambda, y) of T_k:
+    // the Ritz value and its residual norm. With prepare the state becomes
+    // sum_j y_j v_j at unit norm (global sign free), so that calling again is
+    // a plain restarted Lanczos; without it the state is bit-identical.
+    virtual std::pair<double, double> LanczosGroundState(
+        const std::vector<PauliTerm>& terms, int dim = 32, bool prepare = false);
     // product observable squares to identity: Var = 1 - E^2
     double PauliProductVariance(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis)
     {

@@ -63,6 +63,19 @@ public:
     {
         throw QrackError("AdjointGradient: not defined under gate noise");
     }
+    // a Krylov step is no sequence of gates a noise channel could follow: the
+    // two mutating forms are refused, LanczosTridiagonal and the read-only
+    // LanczosGroundState are the wrapper's plain forwards
+    double KrylovEvolvePauliSum(const std::vector<PauliTerm>&, double, int = 16, int = 1) override
+    {
+        throw QrackError("KrylovEvolvePauliSum: not defined under gate noise");
+    }
+    std::pair<double, double> LanczosGroundState(
+        const std::vector<PauliTerm>& t, int dim = 32, bool prepare = false) override
+    {
+        if (prepare) throw QrackError("LanczosGroundState(prepare): not defined under gate noise");
+        return inner->LanczosGroundState(t, dim, false);
+    }
 
     void Mtrx(const cplx<R>* m, bitLenInt t) override
     {

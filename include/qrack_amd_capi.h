@@ -118,6 +118,26 @@ void qrack_pauli_sum_braket(quid sid, quid bra, uint64_t nTerms, const double* c
  * and precision and is not sid */
 void qrack_pauli_sum_apply_into(quid sid, uint64_t nTerms, const double* coeffs,
     const uint64_t* termLens, const uint64_t* qs, const int* paulis, quid dest);
+/* Krylov calls, H laid out as for qrack_evolve_pauli_sum. No
+ * re-orthogonalisation; 1 <= dim <= 64. An error (qrack_get_error(sid))
+ * returns 0.
+ * k <= dim Lanczos steps from the current state, which is left untouched:
+ * alpha and beta (room for dim doubles each) receive alpha_1..k and
+ * beta_2..k+1; returns k */
+uint64_t qrack_lanczos_tridiagonal(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, int dim, double* alpha,
+    double* beta);
+/* exp(-i time H) by Krylov projection, `steps` steps of `dim` Lanczos vectors;
+ * returns the summed a-posteriori error estimate. The dense engines need
+ * dim + 1 states of memory */
+double qrack_krylov_evolve_pauli_sum(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, double time, int dim,
+    int steps);
+/* lowest Ritz value of `dim` Lanczos steps; *residual receives its residual
+ * norm. prepare != 0 leaves the Ritz vector in sid at unit norm */
+double qrack_lanczos_ground_state(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, int dim, int prepare,
+    double* residual);
 
 /* QFT */
 void qrack_qft(quid sid, uint64_t start, uint64_t length);

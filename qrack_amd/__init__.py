@@ -27,6 +27,9 @@ from qrack_amd._qrack import (  # noqa: F401
     pauli_evolve_plan,
     rdm_pass_plan,
     mtrx_n_plan,
+    krylov_coefficients,
+    KRYLOV_MAX_DIM,
+    KRYLOV_COMBINE_MAX_VECTORS,
     MTRXN_MAX,
     RDM_MAX_QUBITS,
     RDM_REG_MAX,
