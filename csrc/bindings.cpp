@@ -1115,6 +1115,43 @@ PYBIND11_MODULE(_qrack, m)
             return out;
         },
         py::arg("length"), py::arg("width"), py::arg("precision"), py::arg("midmax") = 9);
+    // the support-restricted schedule a QFT/IQFT of the basis state |perm> takes
+    m.def(
+        "qft_support_plan",
+        [](int length, int width, const std::string& precision, unsigned long long perm,
+            bool inverse) {
+            if (precision != "fp32" && precision != "fp64") {
+                throw std::invalid_argument("qft_support_plan: precision must be fp32 or fp64");
+            }
+            if (length < 0 || width < length || width > 62) {
+                throw std::invalid_argument("qft_support_plan: need 0 <= length <= width <= 62");
+            }
+            const int realBytes = precision == "fp32" ? 4 : 8;
+            const QftPlanOpts o;
+            const QftSupportPlan sp = qftSupportPlan(qftPassPlan(length, 0, width, realBytes, o),
+                length, 0, width, realBytes, perm, inverse, o.wideLowBits);
+            py::list passes;
+            for (const QftSupportPass& s : sp.passes) {
+                py::dict d;
+                d["kind"] = s.pass.kind == QftPassKind::Low ? "low" : "mid";
+                d["col_lo"] = s.pass.colLo;
+                d["n_cols"] = s.pass.nCols;
+                d["low_bits"] = s.lowBits;
+                d["tile_index_bits"] = s.tileIndexBits;
+                d["fixed_mask"] = s.fixedMask;
+                d["from_buffer"] = s.fromBuffer;
+                d["tile_free"] = s.tileFree;
+                d["tile_fixed"] = s.tileFixed;
+                d["active_tiles"] = s.activeTiles;
+                passes.append(d);
+            }
+            py::dict out;
+            out["eligible"] = sp.eligible;
+            out["passes"] = passes;
+            return out;
+        },
+        py::arg("length"), py::arg("width"), py::arg("precision"), py::arg("perm") = 0ull,
+        py::arg("inverse") = false);
     // the HIP engine's reduced-density-matrix schedule; needs no GPU
     m.def(
         "rdm_pass_plan",

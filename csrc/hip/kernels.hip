@@ -1919,6 +1919,29 @@ template <typename R> __device__ __forceinline__ cplx<R> qaOpaque(cplx<R> a)
     return a;
 }
 
+// Input of a support-restricted pass (QftSupportArgs) at global index x,
+// *elem being sv[x]: the load is predicated, memory outside the support is
+// never read.
+template <typename R>
+__device__ __forceinline__ cplx<R> qaSupportLoad(
+    const cplx<R>* elem, bitCapInt x, const QftSupportArgs& sup, cplx<R> phase)
+{
+    cplx<R> a{ (R)0, (R)0 };
+    if (((x ^ sup.perm) & sup.fixedMask) == 0u) a = sup.fromBuffer ? *elem : phase;
+    return a;
+}
+
+// c-th active tile of a support-restricted pass: the bits of c deposited
+// into the set bits of freeMask, lowest first, over the fixed bits
+__device__ __forceinline__ bitCapInt qaSupportTile(bitCapInt c, bitCapInt freeMask, bitCapInt fixed)
+{
+    bitCapInt t = fixed;
+    for (bitCapInt m = freeMask; m; m &= m - 1u, c >>= 1u) {
+        if (c & 1u) t |= m & (~m + 1u);
+    }
+    return t;
+}
+
 // One group of K columns applied over a 2^tb-amplitude tile as 16-amp
 // register orbits. K is a template parameter so v[] stays in registers
 // (runtime K forces the array to scratch — measured 2.5x slower). Groups
@@ -1930,10 +1953,14 @@ template <typename R> __device__ __forceinline__ cplx<R> qaOpaque(cplx<R> a)
 // (idxBase = the tile's first global index) instead of loading them; the
 // arithmetic, zeros included, is unchanged. SUMS: a toGlobal scatter also
 // adds the norm of every amplitude it stores into `acc`.
-template <typename R, int K, bool PRE, bool BASIS = false, bool SUMS = false>
+//
+// MASKED: a support-restricted pass — the fromGlobal gather goes through
+// qaSupportLoad (phase or a predicated load inside the support, +0 outside).
+template <typename R, int K, bool PRE, bool BASIS = false, bool SUMS = false, bool MASKED = false>
 __device__ __forceinline__ void qftLowGroup(cplx<R>* svBase, cplx<R>* lds, int tile, int gLo,
     R scaleHi, R iSign, bool fromGlobal, bool toGlobal, bitCapInt idxBase = 0u,
-    bitCapInt perm = 0u, cplx<R> phase = cplx<R>{ (R)0, (R)0 }, double* acc = nullptr)
+    bitCapInt perm = 0u, cplx<R> phase = cplx<R>{ (R)0, (R)0 }, double* acc = nullptr,
+    const QftSupportArgs* sup = nullptr)
 {
     constexpr int NS = 1 << K;
     const int orbitCount = tile >> K;
@@ -1942,7 +1969,14 @@ __device__ __forceinline__ void qftLowGroup(cplx<R>* svBase, cplx<R>* lds, int t
         const int r = ((o >> gLo) << (gLo + K)) | below;
         cplx<R> v[NS];
         if (fromGlobal) {
-            if (BASIS) {
+            if (MASKED) {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) {
+                    const int j = r | (b << gLo);
+                    v[b] = qaOpaque<R>(
+                        qaSupportLoad<R>(svBase + j, idxBase | (bitCapInt)j, *sup, phase));
+                }
+            } else if (BASIS) {
 #pragma unroll
                 for (int b = 0; b < NS; ++b) {
                     v[b] = qaOpaque<R>(((idxBase | (bitCapInt)(r | (b << gLo))) == perm)
@@ -2158,16 +2192,121 @@ void launchQftLowLdsSums(cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, d
         tileSumsDev);
 }
 
+// k_qft_low_lds as a support-restricted pass (QftSupportArgs): the loop of
+// k_qft_low_lds_var over the active tiles only, its source masked to the
+// support. A sibling once more, so the kernels above compile as before.
+template <typename R, int K, bool PRE, bool SUMS>
+__global__ void __launch_bounds__(256, 3) k_qft_low_lds_sup(cplx<R>* sv, int tb, int colMax,
+    R piSign, QftSupportArgs sup, cplx<R> phase, double* tileSums)
+{
+    // REQUIRES colMax+1 to be a multiple of K, as k_qft_low_lds does
+    extern __shared__ unsigned char qa_lds_raw[];
+    cplx<R>* lds = reinterpret_cast<cplx<R>*>(qa_lds_raw);
+    const int tile = 1 << tb;
+    const int nCols = colMax + 1;
+    const int nG = nCols / K;
+    const R iSign = (piSign >= 0) ? (R)1 : (R)-1;
+    const int firstG = PRE ? 0 : (nG - 1);
+    const int lastG = PRE ? (nG - 1) : 0;
+    const bool copyIn = (K * firstG) < 6;
+    const bool copyOut = (K * lastG) < 6;
+    for (bitCapInt c = blockIdx.x; c < sup.activeTiles; c += gridDim.x) {
+        const bitCapInt t = qaSupportTile(c, sup.tileFree, sup.tileFixed);
+        cplx<R>* svBase = sv + (t << tb);
+        const bitCapInt idxBase = t << tb;
+        double acc = 0;
+        if (copyIn) {
+            for (int j = threadIdx.x; j < tile; j += blockDim.x) {
+                lds[qaSwz(j)] = qaSupportLoad<R>(svBase + j, idxBase | (bitCapInt)j, sup, phase);
+            }
+        }
+        for (int gi = 0; gi < nG; ++gi) {
+            const int g = PRE ? gi : (nG - 1 - gi);
+            const int gLo = K * g;
+            const bool fromGlobal = (gi == 0) && !copyIn;
+            const bool toGlobal = (gi == nG - 1) && !copyOut;
+            const R scaleHi = piSign / (R)(1 << (gLo + K - 1));
+            if (gi != 0 || copyIn) __syncthreads();
+            qftLowGroup<R, K, PRE, false, SUMS, true>(svBase, lds, tile, gLo, scaleHi, iSign,
+                fromGlobal, toGlobal, idxBase, 0u, phase, &acc, &sup);
+        }
+        if (copyOut) {
+            __syncthreads();
+            if (SUMS) {
+                for (int j = threadIdx.x; j < tile; j += blockDim.x) {
+                    const cplx<R> a = lds[qaSwz(j)];
+                    svBase[j] = a;
+                    acc += (double)norm(a);
+                }
+            } else {
+                for (int j = threadIdx.x; j < tile; j += blockDim.x) svBase[j] = lds[qaSwz(j)];
+            }
+        }
+        if (SUMS) {
+            // fixed-order block reduction, as in k_qft_low_lds_var
+            __shared__ double waveSums[QA_BLOCK / 64];
+            acc = waveReduceSum(acc);
+            if ((threadIdx.x & 63) == 0) waveSums[threadIdx.x >> 6] = acc;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                double s = 0;
+                for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += waveSums[w];
+                tileSums[t] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// the active tiles of a support-restricted pass must lie inside the state
+static void qaCheckSupportTiles(const QftSupportArgs& sup, bitCapInt nTiles)
+{
+    bitCapInt count = 1u;
+    for (bitCapInt m = sup.tileFree; m; m &= m - 1u) count <<= 1u;
+    if (!nTiles || (nTiles & (nTiles - 1u)) || ((sup.tileFree | sup.tileFixed) & ~(nTiles - 1u))
+        || (sup.tileFree & sup.tileFixed) || sup.activeTiles != count) {
+        throw QrackError("QFT support pass: tile subset outside the state");
+    }
+}
+
+void launchQftLowLdsSupport(cplx<float>* sv, bitCapInt maxQPower, int tb, int colMax, int sign,
+    bool pre, const QftSupportArgs& sup, cplx<float> phase, double* tileSumsDev,
+    hipStream_t stream)
+{
+    constexpr int K = qaLowLadderK<float>();
+    if (tb != qaLdsTileBits<float>() || (colMax + 1) % K || colMax >= tb) {
+        throw QrackError("launchQftLowLdsSupport: ladder outside the tile or not K-aligned");
+    }
+    qaCheckSupportTiles(sup, maxQPower >> tb);
+    if (pre && tileSumsDev) throw QrackError("launchQftLowLdsSupport: norms are forward-only");
+    const size_t ldsBytes = (size_t(1) << tb) * sizeof(cplx<float>);
+    const int grid = (int)std::min<bitCapInt>(sup.activeTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const float piSign = (float)sign * 3.14159265358979323846f;
+    if (pre) {
+        hipLaunchKernelGGL((k_qft_low_lds_sup<float, K, true, false>), dim3(grid), dim3(QA_BLOCK),
+            ldsBytes, stream, sv, tb, colMax, piSign, sup, phase, (double*)nullptr);
+    } else if (tileSumsDev) {
+        hipLaunchKernelGGL((k_qft_low_lds_sup<float, K, false, true>), dim3(grid), dim3(QA_BLOCK),
+            ldsBytes, stream, sv, tb, colMax, piSign, sup, phase, tileSumsDev);
+    } else {
+        hipLaunchKernelGGL((k_qft_low_lds_sup<float, K, false, false>), dim3(grid),
+            dim3(QA_BLOCK), ldsBytes, stream, sv, tb, colMax, piSign, sup, phase,
+            (double*)nullptr);
+    }
+}
+
 // One group of K mid columns over a 64 x 2^nCols 2D tile as 16-amp register
 // orbits (K templated — see qftLowGroup). Every access, LDS or HBM, keeps
 // the 64-value `low` dimension in the lane index, so loads/stores are
 // 512 B-contiguous per slot and LDS is bank-conflict-free without swizzle.
 // BASIS: as in qftLowGroup — a fromGlobal gather is synthesised from the
 // index of the basis state phase·|perm> instead of loaded.
-template <typename R, int K, bool PRE, bool BASIS = false>
+// MASKED: as in qftLowGroup — the gather goes through qaSupportLoad.
+template <typename R, int K, bool PRE, bool BASIS = false, bool MASKED = false>
 __device__ __forceinline__ void qftMidGroup(cplx<R>* sv, cplx<R>* lds, bitCapInt xBase,
     int colLo, int tileAmps, int gLo, R midFixed, R hbScale, R scaleHi, R iSign,
-    bool fromGlobal, bool toGlobal, bitCapInt perm = 0u, cplx<R> phase = cplx<R>{ (R)0, (R)0 })
+    bool fromGlobal, bool toGlobal, bitCapInt perm = 0u, cplx<R> phase = cplx<R>{ (R)0, (R)0 },
+    const QftSupportArgs* sup = nullptr)
 {
     constexpr int NS = 1 << K;
     const int orbitCount = tileAmps >> K;
@@ -2178,7 +2317,14 @@ __device__ __forceinline__ void qftMidGroup(cplx<R>* sv, cplx<R>* lds, bitCapInt
         const int cb0 = ((cbr >> gLo) << (gLo + K)) | cbBelow;
         cplx<R> v[NS];
         if (fromGlobal) {
-            if (BASIS) {
+            if (MASKED) {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) {
+                    const bitCapInt x =
+                        xBase | ((bitCapInt)(cb0 | (b << gLo)) << colLo) | (bitCapInt)low;
+                    v[b] = qaOpaque<R>(qaSupportLoad<R>(sv + x, x, *sup, phase));
+                }
+            } else if (BASIS) {
 #pragma unroll
                 for (int b = 0; b < NS; ++b) {
                     v[b] = qaOpaque<R>(
@@ -2382,10 +2528,12 @@ template <int K, int LB> __device__ __forceinline__ int qaWideRow(int cb)
     return (cb ^ ((cb >> K) & ((1 << (6 - LB)) - 1))) << LB;
 }
 
-template <typename R, int K, bool PRE, bool BASIS, int LB, int THREADS>
+// MASKED: as in qftLowGroup — the gather goes through qaSupportLoad.
+template <typename R, int K, bool PRE, bool BASIS, int LB, int THREADS, bool MASKED = false>
 __device__ __forceinline__ void qftMidGroupWide(cplx<R>* sv, cplx<R>* lds, bitCapInt xBase,
     int colLo, int tileAmps, int gLo, R midFixed, R hbScale, R scaleHi, R iSign,
-    bool fromGlobal, bool toGlobal, bitCapInt perm, cplx<R> phase)
+    bool fromGlobal, bool toGlobal, bitCapInt perm, cplx<R> phase,
+    const QftSupportArgs* sup = nullptr)
 {
     constexpr int NS = 1 << K;
     const int orbitCount = tileAmps >> K;
@@ -2396,7 +2544,14 @@ __device__ __forceinline__ void qftMidGroupWide(cplx<R>* sv, cplx<R>* lds, bitCa
         const int cb0 = ((cbr >> gLo) << (gLo + K)) | cbBelow;
         cplx<R> v[NS];
         if (fromGlobal) {
-            if (BASIS) {
+            if (MASKED) {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) {
+                    const bitCapInt x =
+                        xBase | ((bitCapInt)(cb0 | (b << gLo)) << colLo) | (bitCapInt)low;
+                    v[b] = qaOpaque<R>(qaSupportLoad<R>(sv + x, x, *sup, phase));
+                }
+            } else if (BASIS) {
 #pragma unroll
                 for (int b = 0; b < NS; ++b) {
                     v[b] = qaOpaque<R>(
@@ -2545,6 +2700,160 @@ void launchQftMidWide(cplx<float>* sv, bitCapInt maxQPower, int lowBits, int col
         }
     } else {
         throw QrackError("launchQftMidWide: lowBits must be 4 or 5");
+    }
+}
+
+// k_qft_mid_lds and k_qft_mid_wide as support-restricted passes
+// (QftSupportArgs): the same loops over the active tiles only, the first
+// group's source masked to the support. Siblings, so the kernels above
+// compile as before.
+template <typename R, int K, bool PRE>
+__global__ void __launch_bounds__(256, 3) k_qft_mid_lds_sup(
+    cplx<R>* sv, int colLo, int nCols, R piSign, QftSupportArgs sup, cplx<R> phase)
+{
+    // REQUIRES nCols to be a multiple of K, as k_qft_mid_lds does
+    extern __shared__ unsigned char qa_lds_raw2[];
+    cplx<R>* lds = reinterpret_cast<cplx<R>*>(qa_lds_raw2);
+    const int C = 1 << nCols;
+    const int tileAmps = 64 * C;
+    const int nG = nCols / K;
+    const bitCapInt midMask = (ONE_BCI << (colLo - 6)) - 1u;
+    const R hbScale = (R)(uint64_t)(ONE_BCI << colLo);
+    const R iSign = (piSign >= 0) ? (R)1 : (R)-1;
+    for (bitCapInt c = blockIdx.x; c < sup.activeTiles; c += gridDim.x) {
+        const bitCapInt t = qaSupportTile(c, sup.tileFree, sup.tileFixed);
+        const bitCapInt xBase =
+            ((t >> (colLo - 6)) << (colLo + nCols)) | ((t & midMask) << 6);
+        const R midFixed = (R)(uint64_t)((t & midMask) << 6);
+        for (int gi = 0; gi < nG; ++gi) {
+            const int g = PRE ? gi : (nG - 1 - gi);
+            const int gLo = K * g;
+            const bool fromGlobal = (gi == 0);
+            const bool toGlobal = (gi == nG - 1);
+            const R scaleHi = piSign / (R)(ONE_BCI << (colLo + gLo + K - 1));
+            if (gi != 0) __syncthreads();
+            qftMidGroup<R, K, PRE, false, true>(sv, lds, xBase, colLo, tileAmps, gLo, midFixed,
+                hbScale, scaleHi, iSign, fromGlobal, toGlobal, 0u, phase, &sup);
+        }
+        __syncthreads();
+    }
+}
+
+template <typename R, int K, bool PRE, int LB, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_qft_mid_wide_sup(
+    cplx<R>* sv, int colLo, int nCols, R piSign, QftSupportArgs sup, cplx<R> phase)
+{
+    extern __shared__ unsigned char qa_lds_raw3[];
+    cplx<R>* lds = reinterpret_cast<cplx<R>*>(qa_lds_raw3);
+    const int tileAmps = (1 << LB) << nCols;
+    const int nG = nCols / K;
+    const bitCapInt midMask = (ONE_BCI << (colLo - LB)) - 1u;
+    const R hbScale = (R)(uint64_t)(ONE_BCI << colLo);
+    const R iSign = (piSign >= 0) ? (R)1 : (R)-1;
+    for (bitCapInt c = blockIdx.x; c < sup.activeTiles; c += gridDim.x) {
+        const bitCapInt t = qaSupportTile(c, sup.tileFree, sup.tileFixed);
+        const bitCapInt xBase =
+            ((t >> (colLo - LB)) << (colLo + nCols)) | ((t & midMask) << LB);
+        const R midFixed = (R)(uint64_t)((t & midMask) << LB);
+        for (int gi = 0; gi < nG; ++gi) {
+            const int g = PRE ? gi : (nG - 1 - gi);
+            const int gLo = K * g;
+            const bool fromGlobal = (gi == 0);
+            const bool toGlobal = (gi == nG - 1);
+            const R scaleHi = piSign / (R)(ONE_BCI << (colLo + gLo + K - 1));
+            if (gi != 0) __syncthreads();
+            qftMidGroupWide<R, K, PRE, false, LB, THREADS, true>(sv, lds, xBase, colLo, tileAmps,
+                gLo, midFixed, hbScale, scaleHi, iSign, fromGlobal, toGlobal, 0u, phase, &sup);
+        }
+        __syncthreads();
+    }
+}
+
+template <int K, bool PRE>
+static void launchQftMidLdsSupportOne(cplx<float>* sv, int colLo, int nCols, float piSign,
+    const QftSupportArgs& sup, cplx<float> phase, hipStream_t stream)
+{
+    const size_t ldsBytes = (size_t(64) << nCols) * sizeof(cplx<float>);
+    const int grid = (int)std::min<bitCapInt>(sup.activeTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    hipLaunchKernelGGL((k_qft_mid_lds_sup<float, K, PRE>), dim3(grid), dim3(QA_BLOCK), ldsBytes,
+        stream, sv, colLo, nCols, piSign, sup, phase);
+}
+
+template <int K, bool PRE, int LB, int THREADS>
+static void launchQftMidWideSupportOne(cplx<float>* sv, int colLo, int nCols, float piSign,
+    const QftSupportArgs& sup, cplx<float> phase, hipStream_t stream)
+{
+    const size_t ldsBytes = (size_t(1) << (LB + nCols)) * sizeof(cplx<float>);
+    const int grid = (int)std::min<bitCapInt>(sup.activeTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    auto kern = k_qft_mid_wide_sup<float, K, PRE, LB, THREADS>;
+    if (ldsBytes >= 64u * 1024u) {
+        // raise the dynamic-LDS limit once per instantiation and device, as
+        // launchQftMidWideOne does
+        static std::mutex mtx;
+        static std::vector<int> raised;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) throw QrackError("k_qft_mid_wide_sup: no device");
+        std::lock_guard<std::mutex> lock(mtx);
+        if (std::find(raised.begin(), raised.end(), dev) == raised.end()) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes) != hipSuccess) {
+                throw QrackError("k_qft_mid_wide_sup: cannot raise the dynamic LDS limit");
+            }
+            raised.push_back(dev);
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), ldsBytes, stream, sv, colLo, nCols, piSign,
+        sup, phase);
+}
+
+template <int LB>
+static void launchQftMidWideSupportLB(cplx<float>* sv, int colLo, int nCols, float piSign,
+    bool pre, const QftSupportArgs& sup, cplx<float> phase, hipStream_t stream)
+{
+    // block sizes of launchQftMidWideLB
+    constexpr int T9 = 32 << LB;
+    constexpr int T8 = 16 << LB;
+    if (nCols == 9) {
+        if (pre) {
+            launchQftMidWideSupportOne<3, true, LB, T9>(sv, colLo, nCols, piSign, sup, phase, stream);
+        } else {
+            launchQftMidWideSupportOne<3, false, LB, T9>(sv, colLo, nCols, piSign, sup, phase, stream);
+        }
+    } else {
+        if (pre) {
+            launchQftMidWideSupportOne<4, true, LB, T8>(sv, colLo, nCols, piSign, sup, phase, stream);
+        } else {
+            launchQftMidWideSupportOne<4, false, LB, T8>(sv, colLo, nCols, piSign, sup, phase, stream);
+        }
+    }
+}
+
+void launchQftMidSupport(cplx<float>* sv, bitCapInt maxQPower, int lowBits, int colLo, int nCols,
+    int sign, bool pre, const QftSupportArgs& sup, cplx<float> phase, hipStream_t stream)
+{
+    const bool wide = nCols >= 8;
+    if (nCols < 2 || nCols > 9 || nCols == 7 || nCols == 5 || colLo < lowBits
+        || (maxQPower >> (colLo + nCols)) == 0u || (wide ? (lowBits != 4 && lowBits != 5) : lowBits != 6)) {
+        throw QrackError("launchQftMidSupport: columns or run length outside what the kernels take");
+    }
+    qaCheckSupportTiles(sup, maxQPower >> (lowBits + nCols));
+    const float piSign = (float)sign * 3.14159265358979323846f;
+    if (wide) {
+        if (lowBits == 4) {
+            launchQftMidWideSupportLB<4>(sv, colLo, nCols, piSign, pre, sup, phase, stream);
+        } else {
+            launchQftMidWideSupportLB<5>(sv, colLo, nCols, piSign, pre, sup, phase, stream);
+        }
+    } else if ((nCols & 3) == 0) {
+        // same group-width choice as launchQftMidLds
+        if (pre) launchQftMidLdsSupportOne<4, true>(sv, colLo, nCols, piSign, sup, phase, stream);
+        else launchQftMidLdsSupportOne<4, false>(sv, colLo, nCols, piSign, sup, phase, stream);
+    } else if ((nCols % 3) == 0) {
+        if (pre) launchQftMidLdsSupportOne<3, true>(sv, colLo, nCols, piSign, sup, phase, stream);
+        else launchQftMidLdsSupportOne<3, false>(sv, colLo, nCols, piSign, sup, phase, stream);
+    } else {
+        if (pre) launchQftMidLdsSupportOne<2, true>(sv, colLo, nCols, piSign, sup, phase, stream);
+        else launchQftMidLdsSupportOne<2, false>(sv, colLo, nCols, piSign, sup, phase, stream);
     }
 }
 

@@ -401,6 +401,35 @@ void launchQftMidLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols
 void launchQftMidWide(cplx<float>* sv, bitCapInt maxQPower, int lowBits, int colLo, int nCols,
     int sign, bool pre, bool basis, bitCapInt perm, cplx<float> phase, hipStream_t stream);
 
+// Support-restricted passes of a transform of the basis state phase·|perm>
+// (schedule: qftSupportPlan in qft_plan.hpp), fp32 only. The input of the
+// pass can be nonzero only where ((x ^ perm) & fixedMask) == 0; there it is
+// `phase` (fromBuffer = 0) or sv[x] (fromBuffer != 0), everywhere else +0 and
+// the buffer is NOT read: outside the support it holds nothing defined. The
+// pass visits the activeTiles tiles whose index is tileFixed with the bits of
+// tileFree counted through, and writes each of them whole; the stores are
+// bit-identical to the normal kernel's on the materialised state wherever
+// that state is nonzero.
+struct QftSupportArgs {
+    bitCapInt perm;
+    bitCapInt fixedMask;
+    bitCapInt tileFree;
+    bitCapInt tileFixed;
+    bitCapInt activeTiles; // 2^popcount(tileFree)
+    int fromBuffer;
+};
+
+// low ladder; tileSumsDev != nullptr (forward only, all tiles active) also
+// leaves the per-tile norms as launchQftLowLdsSums does
+void launchQftLowLdsSupport(cplx<float>* sv, bitCapInt maxQPower, int tb, int colMax, int sign,
+    bool pre, const QftSupportArgs& sup, cplx<float> phase, double* tileSumsDev,
+    hipStream_t stream);
+
+// mid pass: nCols in {2, 3, 4, 6} on the 64-wide tile, 8 or 9 on the wide
+// one with 2^lowBits-amplitude runs (as launchQftMidLds / launchQftMidWide)
+void launchQftMidSupport(cplx<float>* sv, bitCapInt maxQPower, int lowBits, int colLo, int nCols,
+    int sign, bool pre, const QftSupportArgs& sup, cplx<float> phase, hipStream_t stream);
+
 // forward low ladder that also writes tileSumsDev[t] = sum |amp|^2 of the
 // 2^tb amplitudes it stored for tile t (maxQPower >> tb doubles; fixed
 // reduction order, no atomics)

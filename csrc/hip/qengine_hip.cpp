@@ -1108,6 +1108,70 @@ static const QftPlanOpts& qftPlanOpts()
     return opts;
 }
 
+// QRACK_GPU_QFT_SUPPORT=0: a transform of a pending basis state synthesises
+// only its first pass and sweeps the whole state in every pass
+static bool qaQftSupport()
+{
+    static const bool v = qaEnvSwitch("QRACK_GPU_QFT_SUPPORT");
+    return v;
+}
+
+template <typename R>
+bool QEngineHIP<R>::qftFromBasis(const std::vector<QftPass>& plan, bool inverse, int wideLowBits)
+{
+    // The state is basisPhase_·|basisPerm_> and stays a product state under
+    // every column, so each pass but the last runs only the tiles that can
+    // hold a nonzero amplitude and reads the buffer only inside that support
+    // (qft_plan.hpp). All passes are enqueued here with no rState()/wState()
+    // in between: those would materialise the basis state over the buffer.
+    // basisPending_ is dropped after the last enqueue, so a throw on the way
+    // leaves the engine pending and correct.
+    if constexpr (sizeof(R) == 4) {
+        if (!basisPending_ || !qaQftSupport()) return false;
+        const QftSupportPlan sp = qftSupportPlan(plan, (int)qubitCount, 0, (int)qubitCount,
+            (int)sizeof(R), (unsigned long long)basisPerm_, inverse, wideLowBits);
+        if (!sp.eligible) return false;
+        const int tb = qaLdsTileBits<R>();
+        const int sign = inverse ? -1 : +1;
+        bool sumsLeft = false;
+        for (size_t k = 0; k < sp.passes.size(); ++k) {
+            const QftSupportPass& s = sp.passes[k];
+            QftSupportArgs a{};
+            a.perm = basisPerm_;
+            a.fixedMask = (bitCapInt)s.fixedMask;
+            a.tileFree = (bitCapInt)s.tileFree;
+            a.tileFixed = (bitCapInt)s.tileFixed;
+            a.activeTiles = (bitCapInt)s.activeTiles;
+            a.fromBuffer = s.fromBuffer ? 1 : 0;
+            if (s.pass.kind == QftPassKind::Low) {
+                HipProfScope prof("qft_low_lds", stream);
+                // a forward last pass leaves the per-tile norms, under the
+                // condition of the unrestricted path
+                double* sums = nullptr;
+                if (!inverse && k + 1 == sp.passes.size() && tileSumsUsable()
+                    && maxQPower >= (ONE_BCI << (tb + 11))) {
+                    sums = tileSumsBuffer();
+                    sumsLeft = true;
+                }
+                launchQftLowLdsSupport(dState_, maxQPower, tb, s.pass.colLo + s.pass.nCols - 1, sign,
+                    inverse, a, basisPhase_, sums, stream);
+            } else {
+                HipProfScope prof("qft_mid_lds", stream);
+                launchQftMidSupport(dState_, maxQPower, s.lowBits, s.pass.colLo, s.pass.nCols, sign,
+                    inverse, a, basisPhase_, stream);
+            }
+        }
+        basisPending_ = false;
+        tileSumsValid_ = sumsLeft;
+        return true;
+    } else {
+        (void)plan;
+        (void)inverse;
+        (void)wideLowBits;
+        return false;
+    }
+}
+
 template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length, bool)
 {
     // Walks the planner's pass list (qft_plan.hpp) top column first. Every
@@ -1119,7 +1183,12 @@ template <typename R> void QEngineHIP<R>::QFT(bitLenInt start, bitLenInt length,
     QA_HIP_CHECK(hipSetDevice(deviceId));
     const QftPlanOpts& opts = qftPlanOpts();
     const int tb = qaLdsTileBits<R>();
-    for (const QftPass& p : qftPassPlan((int)length, (int)start, (int)qubitCount, (int)sizeof(R), opts)) {
+    const std::vector<QftPass> plan =
+        qftPassPlan((int)length, (int)start, (int)qubitCount, (int)sizeof(R), opts);
+    if (basisPending_ && !start && length == qubitCount && qftFromBasis(plan, false, opts.wideLowBits)) {
+        return;
+    }
+    for (const QftPass& p : plan) {
         const bitLenInt lo = (bitLenInt)p.colLo;
         const bitLenInt col = (bitLenInt)(p.colLo + p.nCols - 1);
         if (p.kind == QftPassKind::Low) {
@@ -1195,6 +1264,9 @@ template <typename R> void QEngineHIP<R>::IQFT(bitLenInt start, bitLenInt length
     const int tb = qaLdsTileBits<R>();
     const std::vector<QftPass> plan =
         qftPassPlan((int)length, (int)start, (int)qubitCount, (int)sizeof(R), opts);
+    if (basisPending_ && !start && length == qubitCount && qftFromBasis(plan, true, opts.wideLowBits)) {
+        return;
+    }
     for (auto it = plan.rbegin(); it != plan.rend(); ++it) {
         const QftPass& p = *it;
         const bitLenInt lo = (bitLenInt)p.colLo;

@@ -16,6 +16,7 @@
 
 #include "../qengine.hpp"
 #include "kernels.hpp"
+#include "qft_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -400,6 +401,9 @@ protected:
 
 private:
     void materialize(); // pending basis state -> real buffer (memset + one amplitude)
+    // whole QFT/IQFT of a pending basis state as support-restricted passes
+    // (qftSupportPlan); false, with nothing done, where that does not apply
+    bool qftFromBasis(const std::vector<QftPass>& plan, bool inverse, int wideLowBits);
     void setStateBuffer(cplx<R>* buf); // adopt a new buffer (contents defined by the caller)
     double* tileSumsBuffer();          // lazily allocated, maxQPower >> tile bits doubles
     void releaseTileSums();

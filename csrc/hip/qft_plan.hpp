@@ -156,4 +156,92 @@ inline std::vector<QftPass> qftPassPlan(
     return plan;
 }
 
+// ---- support-restricted passes of a transform applied to a basis state ------
+//
+// A QFT column is an H and a phase ladder controlled by lower bits; applied to
+// phase·|p> the state stays a product state, so after the columns C of some
+// passes an amplitude x can be nonzero only where ((x ^ p) & ~F) == 0, F the
+// union of those C ("free" bits). A pass then has to visit only the tiles
+// whose tile-index bits outside F equal p's, and to take its first-group input
+// from the buffer only inside that support (+0 elsewhere). Every pass but the
+// last writes its active tiles whole; the last visits every tile, so the
+// buffer is fully defined on return.
+
+struct QftSupportPass {
+    QftPass pass;
+    int lowBits;             // contiguous-run bits of the pass's tile
+    int tileIndexBits;       // width - tile bits
+    unsigned long long fixedMask; // ~F on entry: input nonzero only where ((x ^ p) & fixedMask) == 0
+    bool fromBuffer;         // F non-empty on entry: in-support input is loaded, not basisPhase
+    unsigned long long tileFree;  // tile-index bits the pass iterates over
+    unsigned long long tileFixed; // value of the other tile-index bits
+    unsigned long long activeTiles; // 2^popcount(tileFree)
+};
+
+struct QftSupportPlan {
+    bool eligible = false;
+    std::vector<QftSupportPass> passes; // in execution order
+};
+
+namespace qftplan {
+
+// tile index of amplitude x (or of a mask of x bits) in a pass's tiling
+inline unsigned long long tileIndexOf(
+    unsigned long long x, const QftPass& p, int lowBits)
+{
+    if (p.kind == QftPassKind::Low) return x >> lowBits;
+    const unsigned long long midMask = (1ull << (p.colLo - lowBits)) - 1ull;
+    return ((x >> (p.colLo + p.nCols)) << (p.colLo - lowBits)) | ((x >> lowBits) & midMask);
+}
+
+} // namespace qftplan
+
+// Support schedule of `plan` (from qftPassPlan, forward order) run forwards
+// or, inverse, backwards on phase·|perm>. Eligible only for a start-0
+// full-width transform of at least two passes, all of them Low or Mid.
+inline QftSupportPlan qftSupportPlan(const std::vector<QftPass>& plan, int length, int start,
+    int width, int realBytes, unsigned long long perm, bool inverse, int wideLowBits = 4)
+{
+    QftSupportPlan out;
+    // (mid passes, and so every multi-pass plan without a Col pass, are fp32-only)
+    if (realBytes != 4 || start != 0 || length != width || width >= 63 || plan.size() < 2u) {
+        return out;
+    }
+    for (const QftPass& p : plan) {
+        if (p.kind != QftPassKind::Low && p.kind != QftPassKind::Mid) return out;
+    }
+    const int tb = realBytes == 4 ? 12 : 11;
+    const unsigned long long all = (1ull << width) - 1ull;
+    unsigned long long freeBits = 0;
+    const size_t n = plan.size();
+    for (size_t k = 0; k < n; ++k) {
+        const QftPass& p = inverse ? plan[n - 1 - k] : plan[k];
+        QftSupportPass s;
+        s.pass = p;
+        s.lowBits = p.kind == QftPassKind::Low ? tb
+            : p.nCols >= QA_QFT_WIDE_MIN_COLS  ? wideLowBits
+                                               : QA_QFT_MID_LOWBITS;
+        const int tileBits = p.kind == QftPassKind::Low ? tb : s.lowBits + p.nCols;
+        if (tileBits > width || (p.kind == QftPassKind::Mid && p.colLo < s.lowBits)) {
+            return QftSupportPlan();
+        }
+        s.tileIndexBits = width - tileBits;
+        s.fixedMask = all & ~freeBits;
+        s.fromBuffer = freeBits != 0;
+        const unsigned long long allTiles = (1ull << s.tileIndexBits) - 1ull;
+        if (k + 1 == n) {
+            s.tileFree = allTiles;
+            s.tileFixed = 0;
+        } else {
+            s.tileFree = qftplan::tileIndexOf(freeBits, p, s.lowBits) & allTiles;
+            s.tileFixed = qftplan::tileIndexOf(perm & all, p, s.lowBits) & allTiles & ~s.tileFree;
+        }
+        s.activeTiles = 1ull << __builtin_popcountll(s.tileFree);
+        out.passes.push_back(s);
+        freeBits |= ((1ull << p.nCols) - 1ull) << p.colLo;
+    }
+    out.eligible = true;
+    return out;
+}
+
 } // namespace qrack_amd
