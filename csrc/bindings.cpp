@@ -1152,6 +1152,26 @@ PYBIND11_MODULE(_qrack, m)
         },
         py::arg("length"), py::arg("width"), py::arg("precision"), py::arg("perm") = 0ull,
         py::arg("inverse") = false);
+    // which orbits of the forward last low pass of such a transform hold a nonzero
+    m.def(
+        "qft_sparse_last_plan",
+        [](int nCols, unsigned long long perm) {
+            const QftSparseLastPlan sp = qftSparseLastPlan(nCols, perm);
+            py::list groups;
+            for (const QftSparseLastGroup& g : sp.groups) {
+                py::dict d;
+                d["g_lo"] = g.gLo;
+                d["real_orbits"] = g.realOrbits;
+                d["below"] = g.below;
+                d["slot"] = g.slot;
+                groups.append(d);
+            }
+            py::dict out;
+            out["eligible"] = sp.eligible;
+            out["groups"] = groups;
+            return out;
+        },
+        py::arg("n_cols"), py::arg("perm") = 0ull);
     // the HIP engine's reduced-density-matrix schedule; needs no GPU
     m.def(
         "rdm_pass_plan",

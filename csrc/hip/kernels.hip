@@ -11,6 +11,7 @@
 //  - the entire ALU family is ONE uniform-opcode permutation kernel (the
 //    branch is wave-uniform) instead of 26 near-identical kernels.
 #include "kernels.hpp"
+#include "qft_plan.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2292,6 +2293,276 @@ void launchQftLowLdsSupport(cplx<float>* sv, bitCapInt maxQPower, int tb, int co
         hipLaunchKernelGGL((k_qft_low_lds_sup<float, K, false, false>), dim3(grid),
             dim3(QA_BLOCK), ldsBytes, stream, sv, tb, colMax, piSign, sup, phase,
             (double*)nullptr);
+    }
+}
+
+// ---- forward last low pass of a support plan: orbits with a nonzero only -----
+//
+// Entering this pass a tile holds one nonzero (12 columns) or sixteen (8
+// columns), so in the first group one orbit in 256 has a nonzero input, in the
+// next 16 in 256, and only the group at gLo = 0 all of them
+// (qftSparseLastPlan). An orbit of sixteen +0 inputs is not dropped for +0
+// outputs: its twiddles have signs, so it leaves signed zeros, and a later
+// orbit with a nonzero input meets them (x·(+0) − y·(−0) and the like decide
+// the sign of a zero component that is stored). Those zeros depend on the
+// in-tile position alone. k_qft_sparse_zero_template runs the dense group
+// code over a tile of +0 and keeps the two sign bits of every amplitude after
+// each group but the last; k_qft_low_sparse_last runs the orbits with a
+// nonzero input alone, takes their fifteen partners from that template, and
+// so stores what k_qft_low_lds_sup stores, bit for bit. That rests on the
+// compiler forming the same contracted arithmetic in both, which it does
+// only for the same code shape: both kernels keep the dense loop and group
+// body statement for statement (tests/test_qft_sparse_last_gpu.py and the
+// byte comparisons of the support and lazy tests are the check).
+
+constexpr int QA_SPARSE_THREADS = 256;
+
+// per group in execution order: qftSparseLastPlan's below and slot
+struct QftSparseLastArgs {
+    int below[3];
+    int slot[3];
+};
+
+// amplitude b of a template mask: bit 2b is the sign of re, bit 2b+1 of im
+__device__ __forceinline__ cplx<float> qaSignedZero(uint32_t m, int b)
+{
+    return cplx<float>{ __uint_as_float((m << (31 - 2 * b)) & 0x80000000u),
+        __uint_as_float((m << (30 - 2 * b)) & 0x80000000u) };
+}
+
+// tpl[g * 4096 + j], g = 0 / 1: sign bits (1: re, 2: im) of amplitude j, on
+// entry to the group at gLo = 4 / gLo = 0 of an nG-group ladder, of a tile
+// outside the support. The loop is k_qft_low_lds_sup's over one such tile
+// (index 1 of a support that fixes every bit to 0: no input matches, none is
+// loaded), without the last group and with the signs kept after each of the
+// others. The group code must see its inputs arrive as in that kernel, from
+// either source: the compiler contracts the orbit arithmetic differently
+// when only one is left, and the zeros' signs follow the contraction.
+// One block of QA_SPARSE_THREADS threads, one tile of LDS.
+__global__ void __launch_bounds__(QA_SPARSE_THREADS)
+    k_qft_sparse_zero_template(unsigned char* tpl, int nG, float piSign)
+{
+    extern __shared__ unsigned char qa_lds_raw[];
+    cplx<float>* lds = reinterpret_cast<cplx<float>*>(qa_lds_raw);
+    constexpr int K = 4;
+    const int tb = 12;
+    const int tile = 1 << tb;
+    const float iSign = (piSign >= 0) ? 1.0f : -1.0f;
+    const cplx<float> phase{ 0.0f, 0.0f };
+    QftSupportArgs sup{};
+    sup.fixedMask = ~(bitCapInt)0u;
+    sup.fromBuffer = 1;
+    const bitCapInt idxBase = (bitCapInt)1u << tb;
+    cplx<float>* svBase = nullptr; // never dereferenced: no index is in the support
+    const bool copyIn = (K * (nG - 1)) < 6;
+    for (int j = threadIdx.x; j < tile; j += blockDim.x) {
+        if (copyIn) {
+            lds[qaSwz(j)] = qaSupportLoad<float>(svBase + j, idxBase | (bitCapInt)j, sup, phase);
+        }
+        tpl[j] = 0; // the inputs of the first group are +0 themselves
+    }
+    for (int gi = 0; gi + 1 < nG; ++gi) {
+        const int gLo = K * (nG - 1 - gi);
+        const bool fromGlobal = (gi == 0) && !copyIn;
+        const float scaleHi = piSign / (float)(1 << (gLo + K - 1));
+        if (gi != 0 || copyIn) __syncthreads();
+        qftLowGroup<float, K, false, false, false, true>(svBase, lds, tile, gLo, scaleHi, iSign,
+            fromGlobal, false, idxBase, 0u, phase, nullptr, &sup);
+        __syncthreads();
+        unsigned char* dst = tpl + (gi + 3 - nG) * tile;
+        for (int j = threadIdx.x; j < tile; j += blockDim.x) {
+            const cplx<float> a = lds[qaSwz(j)];
+            dst[j] = (unsigned char)((__float_as_uint(a.re) >> 31)
+                | ((__float_as_uint(a.im) >> 31) << 1));
+        }
+    }
+}
+
+// qftLowGroup (forward, MASKED) over the orbits with a nonzero input alone:
+// those whose bits under gLo spell `below`, (tile >> K) >> gLo of them. The
+// body is qftLowGroup's, statement for statement, so that the compiler forms
+// the same arithmetic; only the orbit index is spread around `below`.
+template <typename R, int K, bool SUMS>
+__device__ __forceinline__ void qftLowGroupReal(cplx<R>* svBase, cplx<R>* lds, int tile, int gLo,
+    int belowReal, int rot, R scaleHi, R iSign, bool fromGlobal, bool toGlobal, bitCapInt idxBase,
+    cplx<R> phase, double* acc, const QftSupportArgs* sup)
+{
+    constexpr int NS = 1 << K;
+    const int orbitCount = (tile >> K) >> gLo;
+    // (rot: which threads take the few orbits of the first groups)
+    for (int e = (threadIdx.x + rot) & (blockDim.x - 1); e < orbitCount; e += blockDim.x) {
+        const int o = (e << gLo) | belowReal;
+        const int below = o & ((1 << gLo) - 1);
+        const int r = ((o >> gLo) << (gLo + K)) | below;
+        cplx<R> v[NS];
+        if (fromGlobal) {
+#pragma unroll
+            for (int b = 0; b < NS; ++b) {
+                const int j = r | (b << gLo);
+                v[b] = qaOpaque<R>(
+                    qaSupportLoad<R>(svBase + j, idxBase | (bitCapInt)j, *sup, phase));
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < NS; ++b) v[b] = lds[qaSwz(r | (b << gLo))];
+        }
+        R sn, cs;
+        devSinCos<R>(scaleHi * (R)below, &sn, &cs);
+        qftOrbitColumns<R, K, false>(v, iSign, cplx<R>{ cs, sn });
+        if (toGlobal) {
+#pragma unroll
+            for (int b = 0; b < NS; ++b) svBase[r | (b << gLo)] = v[b];
+            if (SUMS) {
+#pragma unroll
+                for (int b = 0; b < NS; ++b) *acc += (double)norm(v[b]);
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < NS; ++b) lds[qaSwz(r | (b << gLo))] = v[b];
+        }
+    }
+}
+
+// k_qft_low_lds_sup's loop for the forward last pass, with two changes. The
+// LDS tile starts every tile as the template: at index j the signed zero a
+// tile outside the support holds there on entry to the group at gLo = 0, or,
+// where j agrees with perm in its low 4 bits (the inputs of the orbits the
+// group at gLo = 4 runs), on entry to that group. And each group runs only
+// the orbits with a nonzero input, in place, so after the last group the tile
+// holds what the dense kernel's holds. The write-out gives every place back
+// to the template as it goes. The copy-in of an 8-column ladder brings in
+// the tile's sixteen in-support amplitudes alone.
+template <bool SUMS>
+__global__ void __launch_bounds__(QA_SPARSE_THREADS, 4) k_qft_low_sparse_last(cplx<float>* sv,
+    int tb, int colMax, float piSign, QftSupportArgs sup, QftSparseLastArgs sch, cplx<float> phase,
+    const unsigned char* zeroTpl, double* tileSums)
+{
+    // REQUIRES tb = 12 and colMax + 1 = 8 or 12 (the launcher checks)
+    constexpr int K = 4;
+    extern __shared__ unsigned char qa_lds_raw[];
+    cplx<float>* lds = reinterpret_cast<cplx<float>*>(qa_lds_raw);
+    const int tile = 1 << tb;
+    const int nCols = colMax + 1;
+    const int nG = nCols / K;
+    const float iSign = (piSign >= 0) ? 1.0f : -1.0f;
+    const int firstG = nG - 1;
+    const bool copyIn = (K * firstG) < 6;
+    const int below4 = sch.below[nG - 2];
+    // the template into LDS; mc keeps the signs for the write-out (bit 2k:
+    // re, bit 2k+1: im of amplitude threadIdx.x + 256 k)
+    uint32_t mc = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int j = (int)threadIdx.x + k * QA_SPARSE_THREADS;
+        const uint32_t bits = zeroTpl[((j & 15) == below4 ? 0 : tile) + j] & 3u;
+        mc |= bits << (2 * k);
+        lds[qaSwz(j)] = qaSignedZero(bits, 0);
+    }
+    __syncthreads(); // the copy-in of the first tile writes into the template
+    for (bitCapInt c = blockIdx.x; c < sup.activeTiles; c += gridDim.x) {
+        const bitCapInt t = qaSupportTile(c, sup.tileFree, sup.tileFixed);
+        cplx<float>* svBase = sv + (t << tb);
+        const bitCapInt idxBase = t << tb;
+        double acc = 0;
+        if (copyIn) {
+            if (threadIdx.x < 16) {
+                const int j = ((int)threadIdx.x << 8) | sch.below[0] | (sch.slot[0] << 4);
+                lds[qaSwz(j)] = qaSupportLoad<float>(svBase + j, idxBase | (bitCapInt)j, sup, phase);
+            }
+        }
+        for (int gi = 0; gi < nG; ++gi) {
+            const int g = nG - 1 - gi;
+            const int gLo = K * g;
+            const bool fromGlobal = (gi == 0) && !copyIn;
+            const bool toGlobal = false; // the group at gLo = 0 goes through LDS
+            const float scaleHi = piSign / (float)(1 << (gLo + K - 1));
+            const int below = gi == 0 ? sch.below[0] : gi == 1 ? sch.below[1] : sch.below[2];
+            __syncthreads();
+            // the one and sixteen orbits of the groups at gLo = 8 and 4 go to a
+            // different wave from group to group, tile to tile and block to
+            // block, so that they do not all queue on one SIMD of the CU
+            const int rot = g ? 64 * (int)((c + (c >> 3) + (c >> 8) + (bitCapInt)gi) & 3u) : 0;
+            qftLowGroupReal<float, K, SUMS>(svBase, lds, tile, gLo, below, rot, scaleHi, iSign,
+                fromGlobal, toGlobal, idxBase, phase, &acc, &sup);
+        }
+        __syncthreads();
+        // the dense write-out loop; sh walks the sign pairs of mc
+        int sh = 31;
+        if (SUMS) {
+            for (int j = threadIdx.x; j < tile; j += blockDim.x) {
+                const cplx<float> a = lds[qaSwz(j)];
+                svBase[j] = a;
+                acc += (double)norm(a);
+                lds[qaSwz(j)] = cplx<float>{ __uint_as_float((mc << sh) & 0x80000000u),
+                    __uint_as_float((mc << (sh - 1)) & 0x80000000u) };
+                sh -= 2;
+            }
+        } else {
+            for (int j = threadIdx.x; j < tile; j += blockDim.x) {
+                svBase[j] = lds[qaSwz(j)];
+                lds[qaSwz(j)] = cplx<float>{ __uint_as_float((mc << sh) & 0x80000000u),
+                    __uint_as_float((mc << (sh - 1)) & 0x80000000u) };
+                sh -= 2;
+            }
+        }
+        if (SUMS) {
+            // fixed-order block reduction, as in k_qft_low_lds_var
+            __shared__ double waveSums[QA_SPARSE_THREADS / 64];
+            acc = waveReduceSum(acc);
+            if ((threadIdx.x & 63) == 0) waveSums[threadIdx.x >> 6] = acc;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                double s = 0;
+                for (int w = 0; w < QA_SPARSE_THREADS / 64; ++w) s += waveSums[w];
+                tileSums[t] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+static float qaForwardPiSign() { return (float)(+1) * 3.14159265358979323846f; }
+
+void launchQftSparseZeroTemplate(unsigned char* zeroTplDev, int nCols, hipStream_t stream)
+{
+    if (!zeroTplDev || (nCols != 8 && nCols != 12)) {
+        throw QrackError("launchQftSparseZeroTemplate: ladder of 8 or 12 columns only");
+    }
+    const size_t ldsBytes = (size_t(1) << 12) * sizeof(cplx<float>);
+    hipLaunchKernelGGL(k_qft_sparse_zero_template, dim3(1), dim3(QA_SPARSE_THREADS), ldsBytes,
+        stream, zeroTplDev, nCols / 4, qaForwardPiSign());
+}
+
+void launchQftLowSparseLast(cplx<float>* sv, bitCapInt maxQPower, int tb, int colMax,
+    const QftSupportArgs& sup, cplx<float> phase, const unsigned char* zeroTplDev,
+    double* tileSumsDev, hipStream_t stream)
+{
+    const int nCols = colMax + 1;
+    const QftSparseLastPlan plan = qftSparseLastPlan(nCols, (unsigned long long)sup.perm);
+    if (tb != 12 || tb != qaLdsTileBits<float>() || qaLowLadderK<float>() != 4 || !plan.eligible) {
+        throw QrackError("launchQftLowSparseLast: ladder of 8 or 12 columns in a 4096-tile only");
+    }
+    qaCheckSupportTiles(sup, maxQPower >> tb);
+    // the nonzeros of a tile must be where the schedule has them
+    const bitCapInt tileMask = ((bitCapInt)1 << tb) - 1u;
+    if ((sup.fixedMask & tileMask) != (((bitCapInt)1 << nCols) - 1u)) {
+        throw QrackError("launchQftLowSparseLast: support does not match the ladder");
+    }
+    if (!zeroTplDev) throw QrackError("launchQftLowSparseLast: no zero template");
+    QftSparseLastArgs sch{};
+    for (size_t g = 0; g < plan.groups.size(); ++g) {
+        sch.below[g] = plan.groups[g].below;
+        sch.slot[g] = plan.groups[g].slot;
+    }
+    const size_t ldsBytes = (size_t(1) << tb) * sizeof(cplx<float>);
+    const int grid = ldsGridFor(sup.activeTiles);
+    const float piSign = qaForwardPiSign();
+    if (tileSumsDev) {
+        hipLaunchKernelGGL((k_qft_low_sparse_last<true>), dim3(grid), dim3(QA_SPARSE_THREADS),
+            ldsBytes, stream, sv, tb, colMax, piSign, sup, sch, phase, zeroTplDev, tileSumsDev);
+    } else {
+        hipLaunchKernelGGL((k_qft_low_sparse_last<false>), dim3(grid), dim3(QA_SPARSE_THREADS),
+            ldsBytes, stream, sv, tb, colMax, piSign, sup, sch, phase, zeroTplDev, tileSumsDev);
     }
 }
 

@@ -425,6 +425,24 @@ void launchQftLowLdsSupport(cplx<float>* sv, bitCapInt maxQPower, int tb, int co
     bool pre, const QftSupportArgs& sup, cplx<float> phase, double* tileSumsDev,
     hipStream_t stream);
 
+// Forward last low pass of a support plan over 8 or 12 columns, running only
+// the 16-point orbits that hold a nonzero input (qftSparseLastPlan in
+// qft_plan.hpp, taken from sup.perm): one, sixteen and 256 per tile instead
+// of 256 in every group. The other orbits transform +0 inputs under twiddles
+// that depend on the position alone, so their outputs are one pattern of
+// signed zeros for every tile: launchQftSparseZeroTemplate leaves it in
+// zeroTplDev (two sign bits per in-tile index and group,
+// QA_QFT_ZERO_TPL_BYTES bytes), and an orbit with a nonzero input takes its
+// fifteen partners from there. The stores and tile sums are bit-identical to
+// launchQftLowLdsSupport's. zeroTplDev must hold the template of the same
+// nCols. One block per tile up to the usual cap; QRACK_GPU_BLOCKS caps the
+// grid further, the blocks then stride over the tiles.
+constexpr size_t QA_QFT_ZERO_TPL_BYTES = 2u << 12;
+void launchQftSparseZeroTemplate(unsigned char* zeroTplDev, int nCols, hipStream_t stream);
+void launchQftLowSparseLast(cplx<float>* sv, bitCapInt maxQPower, int tb, int colMax,
+    const QftSupportArgs& sup, cplx<float> phase, const unsigned char* zeroTplDev,
+    double* tileSumsDev, hipStream_t stream);
+
 // mid pass: nCols in {2, 3, 4, 6} on the 64-wide tile, 8 or 9 on the wide
 // one with 2^lowBits-amplitude runs (as launchQftMidLds / launchQftMidWide)
 void launchQftMidSupport(cplx<float>* sv, bitCapInt maxQPower, int lowBits, int colLo, int nCols,

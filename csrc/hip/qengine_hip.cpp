@@ -155,6 +155,7 @@ template <typename R> QEngineHIP<R>::~QEngineHIP()
     if (dState_) freeDev(dState_, maxQPower);
     releaseScratch();
     releaseTileSums();
+    releaseQftZeroTemplate();
     releaseAux();
     releaseRdm();
     releasePairResults();
@@ -297,6 +298,26 @@ template <typename R> double* QEngineHIP<R>::tileSumsBuffer()
     return dTileSums_;
 }
 
+template <typename R> void QEngineHIP<R>::releaseQftZeroTemplate()
+{
+    if (dQftZeroTpl_) hipFree(dQftZeroTpl_);
+    dQftZeroTpl_ = nullptr;
+    qftZeroTplCols_ = 0;
+}
+
+template <typename R> const unsigned char* QEngineHIP<R>::qftZeroTemplate(int nCols)
+{
+    // the template depends on the ladder length alone, and an engine's plan
+    // ends in one ladder length: formed on first use, on the engine's stream
+    if (!dQftZeroTpl_) QA_HIP_CHECK(hipMalloc(&dQftZeroTpl_, QA_QFT_ZERO_TPL_BYTES));
+    if (qftZeroTplCols_ != nCols) {
+        qftZeroTplCols_ = 0;
+        launchQftSparseZeroTemplate(dQftZeroTpl_, nCols, stream);
+        qftZeroTplCols_ = nCols;
+    }
+    return dQftZeroTpl_;
+}
+
 namespace {
 bool qaEnvSwitch(const char* name)
 {
@@ -340,6 +361,7 @@ template <typename R> void QEngineHIP<R>::SetDevice(int64_t devId)
     GetQuantumState(host.data());
     releaseScratch();
     releaseTileSums();
+    releaseQftZeroTemplate();
     releaseAux();
     releaseRdm();
     releasePairResults();
@@ -1116,6 +1138,14 @@ static bool qaQftSupport()
     return v;
 }
 
+// QRACK_GPU_QFT_SPARSELAST=0: the forward last low pass of such a transform
+// runs every orbit of every tile, zeros included
+static bool qaQftSparseLast()
+{
+    static const bool v = qaEnvSwitch("QRACK_GPU_QFT_SPARSELAST");
+    return v;
+}
+
 template <typename R>
 bool QEngineHIP<R>::qftFromBasis(const std::vector<QftPass>& plan, bool inverse, int wideLowBits)
 {
@@ -1153,8 +1183,17 @@ bool QEngineHIP<R>::qftFromBasis(const std::vector<QftPass>& plan, bool inverse,
                     sums = tileSumsBuffer();
                     sumsLeft = true;
                 }
-                launchQftLowLdsSupport(dState_, maxQPower, tb, s.pass.colLo + s.pass.nCols - 1, sign,
-                    inverse, a, basisPhase_, sums, stream);
+                const bool last = k + 1 == sp.passes.size();
+                if (!inverse && last && (s.pass.nCols == 8 || s.pass.nCols == 12)
+                    && qaQftSparseLast()) {
+                    // only the orbits that hold a nonzero (kernels.hpp)
+                    launchQftLowSparseLast(dState_, maxQPower, tb, s.pass.colLo + s.pass.nCols - 1,
+                        a, basisPhase_, qftZeroTemplate(s.pass.nCols), sums, stream);
+                } else {
+                    launchQftLowLdsSupport(dState_, maxQPower, tb,
+                        s.pass.colLo + s.pass.nCols - 1, sign, inverse, a, basisPhase_, sums,
+                        stream);
+                }
             } else {
                 HipProfScope prof("qft_mid_lds", stream);
                 launchQftMidSupport(dState_, maxQPower, s.lowBits, s.pass.colLo, s.pass.nCols, sign,

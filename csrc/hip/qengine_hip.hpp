@@ -408,6 +408,10 @@ private:
     double* tileSumsBuffer();          // lazily allocated, maxQPower >> tile bits doubles
     void releaseTileSums();
     bool tileSumsUsable() const;       // switch on, no external view taken
+    // signed-zero template of the sparse last QFT pass (kernels.hpp) for an
+    // nCols-column ladder, formed on first use
+    const unsigned char* qftZeroTemplate(int nCols);
+    void releaseQftZeroTemplate();
 
     cplx<R>* dState_ = nullptr;
     // lazy basis state: the state is basisPhase_·|basisPerm_> and the
@@ -420,6 +424,8 @@ private:
     double* dTileSums_ = nullptr;
     bitCapInt tileSumsLen_ = 0;
     bool tileSumsValid_ = false;
+    unsigned char* dQftZeroTpl_ = nullptr;
+    int qftZeroTplCols_ = 0; // ladder length the template holds, 0: none
     bool externView_ = false; // sticky: a raw pointer escaped this engine
     double* dRdm_ = nullptr;
     size_t rdmBytes_ = 0;

@@ -244,4 +244,46 @@ inline QftSupportPlan qftSupportPlan(const std::vector<QftPass>& plan, int lengt
     return out;
 }
 
+// ---- last low pass of a support plan: the orbits that hold a nonzero --------
+//
+// Entering the forward last pass (a low ladder of nCols columns, K = 4 column
+// groups from gLo = nCols-4 down to 0) a tile is nonzero only where the
+// in-tile index agrees with perm in its nCols low bits: one amplitude for 12
+// columns, sixteen for 8. A group's 16-point orbit is the set of indices that
+// differ only in bits gLo..gLo+3; `below` is its bits under gLo. Group by
+// group the nonzeros spread over bits gLo..gLo+3, so in the group at gLo
+// exactly the orbits with below == perm's bits under gLo have a nonzero
+// input, (tile / 16) >> gLo of them per tile, and it sits in slot
+// (perm >> gLo) & 15. Every other orbit transforms sixteen zeros.
+
+struct QftSparseLastGroup {
+    int gLo;        // lowest column of the group
+    int realOrbits; // orbits per tile with a nonzero input
+    int below;      // their `below` value
+    int slot;       // slot of the nonzero input inside each of them
+};
+
+struct QftSparseLastPlan {
+    bool eligible = false;
+    std::vector<QftSparseLastGroup> groups; // in execution order, gLo descending
+};
+
+inline QftSparseLastPlan qftSparseLastPlan(int nCols, unsigned long long perm)
+{
+    constexpr int tb = 12; // fp32 tile bits
+    constexpr int K = 4;   // fp32 ladder group width
+    QftSparseLastPlan out;
+    if (nCols != 8 && nCols != 12) return out;
+    for (int gLo = nCols - K; gLo >= 0; gLo -= K) {
+        QftSparseLastGroup g;
+        g.gLo = gLo;
+        g.realOrbits = (1 << (tb - K)) >> gLo;
+        g.below = (int)(perm & ((1ull << gLo) - 1ull));
+        g.slot = (int)((perm >> gLo) & ((1ull << K) - 1ull));
+        out.groups.push_back(g);
+    }
+    out.eligible = true;
+    return out;
+}
+
 } // namespace qrack_amd

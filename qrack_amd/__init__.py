@@ -25,6 +25,7 @@ from qrack_amd._qrack import (  # noqa: F401
     profile_reset,
     qft_pass_plan,
     qft_support_plan,
+    qft_sparse_last_plan,
     pauli_evolve_plan,
     rdm_pass_plan,
     mtrx_n_plan,
