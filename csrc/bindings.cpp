@@ -1096,17 +1096,23 @@ PYBIND11_MODULE(_qrack, m)
         "[(parity set, tau), ...]) each");
     m.def(
         "qft_pass_plan",
-        [](int length, int width, const std::string& precision, int midmax) {
+        [](int length, int width, const std::string& precision, int midmax, int start, int fuse,
+            bool ldsLow, bool ldsMid) {
             if (precision != "fp32" && precision != "fp64") {
                 throw std::invalid_argument("qft_pass_plan: precision must be fp32 or fp64");
             }
-            if (length < 0 || width < length) {
+            if (length < 0 || start < 0 || width < start + length) {
                 throw std::invalid_argument("qft_pass_plan: need 0 <= length <= width");
             }
+            // the engine's environment switches, as arguments
             QftPlanOpts o;
             o.midMax = midmax;
+            o.fuseMax = fuse;
+            o.ldsLow = ldsLow;
+            o.ldsMid = ldsMid;
             py::list out;
-            for (const QftPass& p : qftPassPlan(length, 0, width, precision == "fp32" ? 4 : 8, o)) {
+            for (const QftPass& p :
+                qftPassPlan(length, start, width, precision == "fp32" ? 4 : 8, o)) {
                 const char* kind = p.kind == QftPassKind::Low ? "low"
                     : p.kind == QftPassKind::Mid              ? "mid"
                                                               : "col";
@@ -1114,7 +1120,9 @@ PYBIND11_MODULE(_qrack, m)
             }
             return out;
         },
-        py::arg("length"), py::arg("width"), py::arg("precision"), py::arg("midmax") = 9);
+        py::arg("length"), py::arg("width"), py::arg("precision"), py::arg("midmax") = 9,
+        py::arg("start") = 0, py::arg("fuse") = 4, py::arg("lds_low") = true,
+        py::arg("lds_mid") = true);
     // the support-restricted schedule a QFT/IQFT of the basis state |perm> takes
     m.def(
         "qft_support_plan",

@@ -68,7 +68,7 @@ static inline int gridFor(bitCapInt n)
 }
 
 // one block per LDS tile, up to QA_MAX_BLOCKS and the QRACK_GPU_BLOCKS cap:
-// the LDS gate-batch kernels loop over the remaining tiles
+// the LDS gate-batch and QFT kernels loop over the remaining tiles
 static inline int ldsGridFor(bitCapInt nTiles)
 {
     bitCapInt b = std::min<bitCapInt>(nTiles, (bitCapInt)QA_MAX_BLOCKS);
@@ -2148,7 +2148,7 @@ void launchQftLowLds(
     constexpr int K = qaLowLadderK<R>();
     const bitCapInt nTiles = maxQPower >> tb;
     const size_t ldsBytes = (size_t(1) << tb) * sizeof(cplx<R>);
-    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const int grid = ldsGridFor(nTiles);
     const R piSign = (R)sign * (R)3.14159265358979323846;
     if (pre) {
         hipLaunchKernelGGL((k_qft_low_lds<R, K, true>), dim3(grid), dim3(QA_BLOCK), ldsBytes,
@@ -2166,7 +2166,7 @@ void launchQftLowLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, 
     constexpr int K = qaLowLadderK<R>();
     const bitCapInt nTiles = maxQPower >> tb;
     const size_t ldsBytes = (size_t(1) << tb) * sizeof(cplx<R>);
-    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const int grid = ldsGridFor(nTiles);
     const R piSign = (R)sign * (R)3.14159265358979323846;
     if (pre) {
         hipLaunchKernelGGL((k_qft_low_lds_var<R, K, true, true, false>), dim3(grid),
@@ -2186,7 +2186,7 @@ void launchQftLowLdsSums(cplx<R>* sv, bitCapInt maxQPower, int tb, int colMax, d
     constexpr int K = qaLowLadderK<R>();
     const bitCapInt nTiles = maxQPower >> tb;
     const size_t ldsBytes = (size_t(1) << tb) * sizeof(cplx<R>);
-    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const int grid = ldsGridFor(nTiles);
     const R piSign = (R)3.14159265358979323846;
     hipLaunchKernelGGL((k_qft_low_lds_var<R, K, false, false, true>), dim3(grid), dim3(QA_BLOCK),
         ldsBytes, stream, sv, nTiles, tb, colMax, piSign, (bitCapInt)0u, cplx<R>{ (R)0, (R)0 },
@@ -2281,7 +2281,7 @@ void launchQftLowLdsSupport(cplx<float>* sv, bitCapInt maxQPower, int tb, int co
     qaCheckSupportTiles(sup, maxQPower >> tb);
     if (pre && tileSumsDev) throw QrackError("launchQftLowLdsSupport: norms are forward-only");
     const size_t ldsBytes = (size_t(1) << tb) * sizeof(cplx<float>);
-    const int grid = (int)std::min<bitCapInt>(sup.activeTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const int grid = ldsGridFor(sup.activeTiles);
     const float piSign = (float)sign * 3.14159265358979323846f;
     if (pre) {
         hipLaunchKernelGGL((k_qft_low_lds_sup<float, K, true, false>), dim3(grid), dim3(QA_BLOCK),
@@ -2709,7 +2709,7 @@ void launchQftMidLds(
 {
     const bitCapInt nTiles = maxQPower >> (6 + nCols);
     const size_t ldsBytes = (size_t(64) << nCols) * sizeof(cplx<R>);
-    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const int grid = ldsGridFor(nTiles);
     const R piSign = (R)sign * (R)3.14159265358979323846;
     // uniform group width: 4 | nCols -> K=4, else 3 | nCols -> K=3 (the
     // engine only requests nCols in {4, 6}; other multiples also work)
@@ -2759,7 +2759,7 @@ void launchQftMidLdsBasis(cplx<R>* sv, bitCapInt maxQPower, int colLo, int nCols
 {
     const bitCapInt nTiles = maxQPower >> (6 + nCols);
     const size_t ldsBytes = (size_t(64) << nCols) * sizeof(cplx<R>);
-    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const int grid = ldsGridFor(nTiles);
     const R piSign = (R)sign * (R)3.14159265358979323846;
     // same group-width choice as launchQftMidLds
     if ((nCols & 3) == 0) {
@@ -2895,7 +2895,7 @@ static void launchQftMidWideOne(cplx<R>* sv, bitCapInt maxQPower, int colLo, int
 {
     const bitCapInt nTiles = maxQPower >> (LB + nCols);
     const size_t ldsBytes = (size_t(1) << (LB + nCols)) * sizeof(cplx<R>);
-    const int grid = (int)std::min<bitCapInt>(nTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const int grid = ldsGridFor(nTiles);
     auto kern = k_qft_mid_wide<R, K, PRE, BASIS, LB, THREADS>;
     if (ldsBytes >= 64u * 1024u) {
         // a tile at or above the default dynamic-LDS limit: raise it, once
@@ -3045,7 +3045,7 @@ static void launchQftMidLdsSupportOne(cplx<float>* sv, int colLo, int nCols, flo
     const QftSupportArgs& sup, cplx<float> phase, hipStream_t stream)
 {
     const size_t ldsBytes = (size_t(64) << nCols) * sizeof(cplx<float>);
-    const int grid = (int)std::min<bitCapInt>(sup.activeTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const int grid = ldsGridFor(sup.activeTiles);
     hipLaunchKernelGGL((k_qft_mid_lds_sup<float, K, PRE>), dim3(grid), dim3(QA_BLOCK), ldsBytes,
         stream, sv, colLo, nCols, piSign, sup, phase);
 }
@@ -3055,7 +3055,7 @@ static void launchQftMidWideSupportOne(cplx<float>* sv, int colLo, int nCols, fl
     const QftSupportArgs& sup, cplx<float> phase, hipStream_t stream)
 {
     const size_t ldsBytes = (size_t(1) << (LB + nCols)) * sizeof(cplx<float>);
-    const int grid = (int)std::min<bitCapInt>(sup.activeTiles, (bitCapInt)QA_REDUCE_MAX_BLOCKS);
+    const int grid = ldsGridFor(sup.activeTiles);
     auto kern = k_qft_mid_wide_sup<float, K, PRE, LB, THREADS>;
     if (ldsBytes >= 64u * 1024u) {
         // raise the dynamic-LDS limit once per instantiation and device, as
