@@ -2378,60 +2378,127 @@ __global__ void __launch_bounds__(QA_SPARSE_THREADS)
     }
 }
 
-// qftLowGroup (forward, MASKED) over the orbits with a nonzero input alone:
-// those whose bits under gLo spell `below`, (tile >> K) >> gLo of them. The
-// body is qftLowGroup's, statement for statement, so that the compiler forms
-// the same arithmetic; only the orbit index is spread around `below`.
-template <typename R, int K, bool SUMS>
-__device__ __forceinline__ void qftLowGroupReal(cplx<R>* svBase, cplx<R>* lds, int tile, int gLo,
-    int belowReal, int rot, R scaleHi, R iSign, bool fromGlobal, bool toGlobal, bitCapInt idxBase,
-    cplx<R> phase, double* acc, const QftSupportArgs* sup)
+// tiles a block of k_qft_low_sparse_last takes at a time, as a power of two
+constexpr int QA_SPARSE_BATCH_LOG2 = 2;
+constexpr int QA_SPARSE_BATCH = 1 << QA_SPARSE_BATCH_LOG2;
+// amplitudes of a tile that the groups at gLo = 8 and gLo = 4 touch
+constexpr int QA_SPARSE_COMPACT = 256;
+
+// the low bits of a batch's tile counter through qaSupportTile's deposit:
+// qaSupportTile(c0 | i) = qaSupportTile(c0) | qaSupportTileLow(i) for
+// c0 a multiple of QA_SPARSE_BATCH and i below it
+__device__ __forceinline__ bitCapInt qaSupportTileLow(int i, bitCapInt freeMask)
+{
+    bitCapInt t = 0u;
+#pragma unroll
+    for (int q = 0; q < QA_SPARSE_BATCH_LOG2; ++q) {
+        if ((i >> q) & 1) t |= freeMask & (~freeMask + 1u);
+        freeMask &= freeMask - 1u;
+    }
+    return t;
+}
+
+// an amplitude in LDS. cplx<float> is aligned to 4 bytes, which makes two
+// 4-byte LDS accesses of it; every place of the images is aligned to 8.
+__device__ __forceinline__ cplx<float> qaLdsGet(const cplx<float>* p)
+{
+    const float2 f = *reinterpret_cast<const float2*>(p);
+    return cplx<float>{ f.x, f.y };
+}
+__device__ __forceinline__ void qaLdsPut(cplx<float>* p, cplx<float> a)
+{
+    *reinterpret_cast<float2*>(p) = make_float2(a.re, a.im);
+}
+
+// qftLowGroup's body (forward, MASKED) for one orbit with a nonzero input.
+// The floating-point statements are qftLowGroup's, statement for statement
+// and with both gather sources, so that the compiler forms the same
+// arithmetic; only the indices differ. The orbit's sixteen places are
+// img[qaSwz(r | (b << sh))]; a fromGlobal gather reads the tile at
+// jr | (b << gLo). `below` is the orbit's index under gLo in the tile.
+template <typename R, int K>
+__device__ __forceinline__ void qftLowGroupReal(cplx<R>* svBase, cplx<R>* img, bool active, int r,
+    int sh, int jr, int gLo, int below, R scaleHi, R iSign, bool fromGlobal, bitCapInt idxBase,
+    cplx<R> phase, const QftSupportArgs* sup)
 {
     constexpr int NS = 1 << K;
-    const int orbitCount = (tile >> K) >> gLo;
-    // (rot: which threads take the few orbits of the first groups)
-    for (int e = (threadIdx.x + rot) & (blockDim.x - 1); e < orbitCount; e += blockDim.x) {
-        const int o = (e << gLo) | belowReal;
-        const int below = o & ((1 << gLo) - 1);
-        const int r = ((o >> gLo) << (gLo + K)) | below;
+    if (active) {
         cplx<R> v[NS];
         if (fromGlobal) {
 #pragma unroll
             for (int b = 0; b < NS; ++b) {
-                const int j = r | (b << gLo);
+                const int j = jr | (b << gLo);
                 v[b] = qaOpaque<R>(
                     qaSupportLoad<R>(svBase + j, idxBase | (bitCapInt)j, *sup, phase));
             }
         } else {
 #pragma unroll
-            for (int b = 0; b < NS; ++b) v[b] = lds[qaSwz(r | (b << gLo))];
+            for (int b = 0; b < NS; ++b) v[b] = qaLdsGet(img + qaSwz(r | (b << sh)));
         }
         R sn, cs;
         devSinCos<R>(scaleHi * (R)below, &sn, &cs);
         qftOrbitColumns<R, K, false>(v, iSign, cplx<R>{ cs, sn });
-        if (toGlobal) {
 #pragma unroll
-            for (int b = 0; b < NS; ++b) svBase[r | (b << gLo)] = v[b];
-            if (SUMS) {
-#pragma unroll
-                for (int b = 0; b < NS; ++b) *acc += (double)norm(v[b]);
-            }
-        } else {
-#pragma unroll
-            for (int b = 0; b < NS; ++b) lds[qaSwz(r | (b << gLo))] = v[b];
-        }
+        for (int b = 0; b < NS; ++b) qaLdsPut(img + qaSwz(r | (b << sh)), v[b]);
     }
 }
 
-// k_qft_low_lds_sup's loop for the forward last pass, with two changes. The
-// LDS tile starts every tile as the template: at index j the signed zero a
-// tile outside the support holds there on entry to the group at gLo = 0, or,
-// where j agrees with perm in its low 4 bits (the inputs of the orbits the
-// group at gLo = 4 runs), on entry to that group. And each group runs only
-// the orbits with a nonzero input, in place, so after the last group the tile
-// holds what the dense kernel's holds. The write-out gives every place back
-// to the template as it goes. The copy-in of an 8-column ladder brings in
-// the tile's sixteen in-support amplitudes alone.
+// |a|^2 as the dense kernels' write-out forms it, both products rounded and
+// then added (there the compiler packs the two multiplications); left to
+// contract, the compiler fuses one product into the addition here and the
+// tile sums lose their last bits
+__device__ __forceinline__ float qaNormUnfused(cplx<float> a)
+{
+#pragma clang fp contract(off)
+    return a.re * a.re + a.im * a.im;
+}
+
+// one wave's LDS traffic in order: what its lanes stored before is what any
+// of its lanes loads after
+__device__ __forceinline__ void qaWaveSync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The forward last pass over the orbits with a nonzero input, T =
+// QA_SPARSE_BATCH tiles at a time. A batch is T consecutive active tiles
+// (qaSupportTile of c0 .. c0 + T - 1); the blocks stride over the batches.
+//
+// LDS: the 4096-amplitude tile image, then T compact images of 256.
+// Between tiles the tile image holds the template: at index j the signed
+// zero a tile outside the support holds there on entry to the group at
+// gLo = 0. The groups at gLo = 8 and gLo = 4 touch only the 256 places
+// with (j & 15) == perm & 15; those live in the tile's compact image at
+// m = j >> 4, which between batches holds the signed zeros on entry to the
+// group at gLo = 4.
+//
+// Stage A, for the whole batch: the T orbits of the group at gLo = 8 in T
+// lanes of one wave (their T loads from HBM leave together; one orbit per
+// wave occupies four SIMDs for the same latency and measured slower), a
+// barrier, the 16 T orbits of the group at gLo = 4 in one wave, a barrier.
+// An 8-column ladder has the copy-in of its 16 T in-support amplitudes
+// instead of the first group. All steps share one inlined orbit body.
+//
+// Stage B, tile by tile with no block barrier: thread o moves its seed
+// compact[o] to place 16 o + (perm & 15) of the tile image, gives the
+// compact place back to its template, and runs orbit o of the group at
+// gLo = 0 on places 16 o .. 16 o + 15. Wave w so owns [1024 w, 1024 w +
+// 1024) and, after a wave-level fence, writes that out by itself,
+// lane-contiguously, putting the template back behind itself. The waves
+// drift apart: one's stores overlap another's arithmetic. (A 16-byte
+// write-out and nontemporal stores were measured and gained nothing that
+// stands clear of the noise: profiles/PROF_QFT_SPARSE_BATCH.md.)
+//
+// Tile sums: every wave keeps its partial of tile i in lane i and leaves it
+// after the batch in a tile-image place that the next seed overwrites
+// anyway; one barrier, then thread i adds the four in wave order. A
+// tile's 4096 norms are fp32 values of nearly one exponent, their sum
+// needs under 40 bits, so every order of summation gives the same double
+// as the dense kernel's.
+//
+// Three block barriers per batch.
 template <bool SUMS>
 __global__ void __launch_bounds__(QA_SPARSE_THREADS, 4) k_qft_low_sparse_last(cplx<float>* sv,
     int tb, int colMax, float piSign, QftSupportArgs sup, QftSparseLastArgs sch, cplx<float> phase,
@@ -2439,85 +2506,142 @@ __global__ void __launch_bounds__(QA_SPARSE_THREADS, 4) k_qft_low_sparse_last(cp
 {
     // REQUIRES tb = 12 and colMax + 1 = 8 or 12 (the launcher checks)
     constexpr int K = 4;
+    constexpr int T = QA_SPARSE_BATCH;
     extern __shared__ unsigned char qa_lds_raw[];
     cplx<float>* lds = reinterpret_cast<cplx<float>*>(qa_lds_raw);
     const int tile = 1 << tb;
+    cplx<float>* compact = lds + tile;
     const int nCols = colMax + 1;
     const int nG = nCols / K;
     const float iSign = (piSign >= 0) ? 1.0f : -1.0f;
-    const int firstG = nG - 1;
-    const bool copyIn = (K * firstG) < 6;
+    const bool copyIn = (K * (nG - 1)) < 6;
+    const int below8 = sch.below[0];
     const int below4 = sch.below[nG - 2];
-    // the template into LDS; mc keeps the signs for the write-out (bit 2k:
-    // re, bit 2k+1: im of amplitude threadIdx.x + 256 k)
+    int tid = (int)threadIdx.x;
+    int lane = tid & 63;
+    int wave = tid >> 6;
+    // the template into LDS. mc keeps the signs of the sixteen places this
+    // thread writes out, in write-out order (bit 2q: re, bit 2q+1: im)
     uint32_t mc = 0;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int j = (int)threadIdx.x + k * QA_SPARSE_THREADS;
-        const uint32_t bits = zeroTpl[((j & 15) == below4 ? 0 : tile) + j] & 3u;
-        mc |= bits << (2 * k);
+    for (int q = 0; q < 16; ++q) {
+        const int j = 1024 * wave + lane + 64 * q;
+        const uint32_t bits = zeroTpl[tile + j] & 3u;
+        mc |= bits << (2 * q);
         lds[qaSwz(j)] = qaSignedZero(bits, 0);
     }
-    __syncthreads(); // the copy-in of the first tile writes into the template
-    for (bitCapInt c = blockIdx.x; c < sup.activeTiles; c += gridDim.x) {
-        const bitCapInt t = qaSupportTile(c, sup.tileFree, sup.tileFixed);
-        cplx<float>* svBase = sv + (t << tb);
-        const bitCapInt idxBase = t << tb;
-        double acc = 0;
+    const uint32_t mseed = zeroTpl[(tid << 4) | below4] & 3u;
+#pragma unroll
+    for (int i = 0; i < T; ++i) compact[QA_SPARSE_COMPACT * i + qaSwz(tid)] = qaSignedZero(mseed, 0);
+    __syncthreads();
+    const bitCapInt nBatches = (sup.activeTiles + (bitCapInt)(T - 1)) >> QA_SPARSE_BATCH_LOG2;
+    for (bitCapInt cb = blockIdx.x; cb < nBatches; cb += gridDim.x) {
+        const bitCapInt c0 = cb << QA_SPARSE_BATCH_LOG2;
+        const int nt = (sup.activeTiles - c0 < (bitCapInt)T) ? (int)(sup.activeTiles - c0) : T;
+        const bitCapInt tHi = qaSupportTile(c0, sup.tileFree, sup.tileFixed);
+        double keep = 0;
+        // what follows from the thread index is formed again where it is
+        // used: kept from ahead of the loops it costs the orbit registers
+        asm volatile("" : "+v"(tid));
         if (copyIn) {
-            if (threadIdx.x < 16) {
-                const int j = ((int)threadIdx.x << 8) | sch.below[0] | (sch.slot[0] << 4);
-                lds[qaSwz(j)] = qaSupportLoad<float>(svBase + j, idxBase | (bitCapInt)j, sup, phase);
+            const int i = tid >> 4;
+            if (i < nt) {
+                const bitCapInt t = tHi | qaSupportTileLow(i, sup.tileFree);
+                const int j = ((tid & 15) << 8) | sch.below[0] | (sch.slot[0] << 4);
+                compact[QA_SPARSE_COMPACT * i + qaSwz(j >> 4)] = qaSupportLoad<float>(
+                    sv + (t << tb) + j, (t << tb) | (bitCapInt)j, sup, phase);
             }
         }
-        for (int gi = 0; gi < nG; ++gi) {
-            const int g = nG - 1 - gi;
-            const int gLo = K * g;
-            const bool fromGlobal = (gi == 0) && !copyIn;
-            const bool toGlobal = false; // the group at gLo = 0 goes through LDS
+        // steps 0 and 1 are stage A, step 2 + i is tile i of stage B
+        for (int st = copyIn ? 1 : 0; st < 2 + nt; ++st) {
+            if (st == 1 || st == 2) __syncthreads();
+            asm volatile("" : "+v"(tid));
+            lane = tid & 63;
+            wave = tid >> 6;
+            // the wave of a stage A step changes from step to step, batch to
+            // batch and block to block, so that they do not all queue on one
+            // SIMD of the CU
+            const int rot = 64 * (int)((cb + (cb >> 3) + (cb >> 8) + (bitCapInt)st) & 3u);
+            const int x = (tid + rot) & (QA_SPARSE_THREADS - 1);
+            int i, r, sh, gLo, below;
+            if (st == 0) {
+                i = x;
+                r = below8 >> 4;
+                sh = 4;
+                gLo = 8;
+                below = below8;
+            } else if (st == 1) {
+                i = x >> 4;
+                r = (x & 15) << 4;
+                sh = 0;
+                gLo = 4;
+                below = below4;
+            } else {
+                i = st - 2;
+                r = tid << 4;
+                sh = 0;
+                gLo = 0;
+                below = 0;
+            }
+            const bool stageB = st >= 2;
+            const bitCapInt t = tHi | qaSupportTileLow(i, sup.tileFree);
+            cplx<float>* svBase = sv + (t << tb);
+            cplx<float>* cimg = compact + QA_SPARSE_COMPACT * i;
+            if (stageB) {
+                const int p = qaSwz(tid);
+                lds[qaSwz(r | below4)] = cimg[p];
+                cimg[p] = qaSignedZero(mseed, 0);
+            }
             const float scaleHi = piSign / (float)(1 << (gLo + K - 1));
-            const int below = gi == 0 ? sch.below[0] : gi == 1 ? sch.below[1] : sch.below[2];
-            __syncthreads();
-            // the one and sixteen orbits of the groups at gLo = 8 and 4 go to a
-            // different wave from group to group, tile to tile and block to
-            // block, so that they do not all queue on one SIMD of the CU
-            const int rot = g ? 64 * (int)((c + (c >> 3) + (c >> 8) + (bitCapInt)gi) & 3u) : 0;
-            qftLowGroupReal<float, K, SUMS>(svBase, lds, tile, gLo, below, rot, scaleHi, iSign,
-                fromGlobal, toGlobal, idxBase, phase, &acc, &sup);
-        }
-        __syncthreads();
-        // the dense write-out loop; sh walks the sign pairs of mc
-        int sh = 31;
-        if (SUMS) {
-            for (int j = threadIdx.x; j < tile; j += blockDim.x) {
-                const cplx<float> a = lds[qaSwz(j)];
-                svBase[j] = a;
-                acc += (double)norm(a);
-                lds[qaSwz(j)] = cplx<float>{ __uint_as_float((mc << sh) & 0x80000000u),
-                    __uint_as_float((mc << (sh - 1)) & 0x80000000u) };
-                sh -= 2;
-            }
-        } else {
-            for (int j = threadIdx.x; j < tile; j += blockDim.x) {
-                svBase[j] = lds[qaSwz(j)];
-                lds[qaSwz(j)] = cplx<float>{ __uint_as_float((mc << sh) & 0x80000000u),
-                    __uint_as_float((mc << (sh - 1)) & 0x80000000u) };
-                sh -= 2;
-            }
-        }
-        if (SUMS) {
-            // fixed-order block reduction, as in k_qft_low_lds_var
-            __shared__ double waveSums[QA_SPARSE_THREADS / 64];
-            acc = waveReduceSum(acc);
-            if ((threadIdx.x & 63) == 0) waveSums[threadIdx.x >> 6] = acc;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                double s = 0;
-                for (int w = 0; w < QA_SPARSE_THREADS / 64; ++w) s += waveSums[w];
-                tileSums[t] = s;
+            qftLowGroupReal<float, K>(svBase, stageB ? lds : cimg, i < nt, r, sh, below8, gLo, below,
+                scaleHi, iSign, st == 0, t << tb, phase, &sup);
+            if (stageB) {
+                qaWaveSync();
+                // (i is uniform here) the write-out, with the signs taken from
+                // mc place by place: formed ahead of the loop they would
+                // cost 32 registers
+                cplx<float>* svOut = sv + ((tHi | qaSupportTileLow(st - 2, sup.tileFree)) << tb);
+                asm volatile("" : "+v"(mc));
+                double acc = 0;
+                int bit = 31;
+                // amplitude k of the lane is j = 1024 wave + lane + 64 k. Bits
+                // 6..9 of j are k and bits 4, 5 come from the lane, so
+                // qaSwz(j) = (qaSwz(j0) ^ 4 (k & 3)) + 64 k: four bases and
+                // constant offsets, in LDS and in the tile
+                const int q0 = qaSwz(1024 * wave + lane);
+                cplx<float>* outLane = svOut + (1024 * wave + lane);
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    cplx<float>* place = lds + (q0 ^ ((k & 3) << 2)) + 64 * k;
+                    const cplx<float> a = qaLdsGet(place);
+                    outLane[64 * k] = a;
+                    if (SUMS) acc += (double)qaNormUnfused(a);
+                    qaLdsPut(place, cplx<float>{ __uint_as_float((mc << bit) & 0x80000000u),
+                        __uint_as_float((mc << (bit - 1)) & 0x80000000u) });
+                    bit -= 2;
+                }
+                qaWaveSync();
+                if (SUMS) {
+                    acc = waveReduceSum(acc);
+                    const double tot = __shfl(acc, 0);
+                    if (lane == i) keep = tot;
+                }
             }
         }
-        __syncthreads();
+        // the partials go where the seeds of the next batch land
+        lane = tid & 63;
+        wave = tid >> 6;
+        if (SUMS && lane < nt) {
+            *reinterpret_cast<double*>(lds + qaSwz(((64 * wave + lane) << 4) | below4)) = keep;
+        }
+        __syncthreads(); // the compact images are free again
+        if (SUMS && tid < nt) {
+            double s = 0;
+            for (int w = 0; w < QA_SPARSE_THREADS / 64; ++w) {
+                s += *reinterpret_cast<const double*>(lds + qaSwz(((64 * w + tid) << 4) | below4));
+            }
+            tileSums[tHi | qaSupportTileLow(tid, sup.tileFree)] = s;
+        }
     }
 }
 
@@ -2554,8 +2678,11 @@ void launchQftLowSparseLast(cplx<float>* sv, bitCapInt maxQPower, int tb, int co
         sch.below[g] = plan.groups[g].below;
         sch.slot[g] = plan.groups[g].slot;
     }
-    const size_t ldsBytes = (size_t(1) << tb) * sizeof(cplx<float>);
-    const int grid = ldsGridFor(sup.activeTiles);
+    // the tile image and one compact image per tile of a batch; nothing
+    // static beside them, so that four blocks share a CU's 160 KB
+    const size_t ldsBytes = ((size_t(1) << tb) + (size_t)QA_SPARSE_BATCH * QA_SPARSE_COMPACT)
+        * sizeof(cplx<float>);
+    const int grid = ldsGridFor((sup.activeTiles + QA_SPARSE_BATCH - 1u) / QA_SPARSE_BATCH);
     const float piSign = qaForwardPiSign();
     if (tileSumsDev) {
         hipLaunchKernelGGL((k_qft_low_sparse_last<true>), dim3(grid), dim3(QA_SPARSE_THREADS),

@@ -435,8 +435,11 @@ void launchQftLowLdsSupport(cplx<float>* sv, bitCapInt maxQPower, int tb, int co
 // QA_QFT_ZERO_TPL_BYTES bytes), and an orbit with a nonzero input takes its
 // fifteen partners from there. The stores and tile sums are bit-identical to
 // launchQftLowLdsSupport's. zeroTplDev must hold the template of the same
-// nCols. One block per tile up to the usual cap; QRACK_GPU_BLOCKS caps the
-// grid further, the blocks then stride over the tiles.
+// nCols. A block takes four consecutive active tiles at a time: the groups
+// at gLo = 8 and gLo = 4 run for the whole batch at once, the group at
+// gLo = 0 and the write-out tile by tile with each wave on its own quarter
+// (kernels.hip). One block per batch up to the usual cap; QRACK_GPU_BLOCKS
+// caps the grid further, the blocks then stride over the batches.
 constexpr size_t QA_QFT_ZERO_TPL_BYTES = 2u << 12;
 void launchQftSparseZeroTemplate(unsigned char* zeroTplDev, int nCols, hipStream_t stream);
 void launchQftLowSparseLast(cplx<float>* sv, bitCapInt maxQPower, int tb, int colMax,
