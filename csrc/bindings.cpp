@@ -634,6 +634,37 @@ template <typename R> static void bindQInterface(py::module_& m, const char* nam
             "(lowest Ritz value, its residual norm) of `dim` Lanczos steps from the current state; "
             "prepare=True leaves the Ritz vector in the simulator at unit norm, so that calling "
             "again is a restarted Lanczos")
+        .def("lanczos_lowest_states",
+            [](QI& q, std::vector<std::tuple<double, std::vector<bitLenInt>, std::vector<int>>> terms,
+                int nev, int dim, double tol, int maxRestarts, int prepare) {
+                const KrylovEigenResult r = q.LanczosLowestStates(
+                    pauliTermsFromTuples(terms, "lanczos_lowest_states"), nev, dim, tol, maxRestarts, prepare);
+                py::array_t<double> v((py::ssize_t)r.values.size()), res((py::ssize_t)r.residuals.size());
+                std::copy(r.values.begin(), r.values.end(), v.mutable_data());
+                std::copy(r.residuals.begin(), r.residuals.end(), res.mutable_data());
+                const py::ssize_t rows = (py::ssize_t)r.restarts + 1;
+                py::array_t<double> hv({ rows, (py::ssize_t)nev }), hr({ rows, (py::ssize_t)nev });
+                std::copy(r.historyValues.begin(), r.historyValues.end(), hv.mutable_data());
+                std::copy(r.historyResiduals.begin(), r.historyResiduals.end(), hr.mutable_data());
+                py::dict info;
+                info["converged"] = r.converged;
+                info["restarts"] = r.restarts;
+                info["applies"] = r.applies;
+                info["history_values"] = hv;
+                info["history_residuals"] = hr;
+                return py::make_tuple(v, res, info);
+            },
+            py::arg("terms"), py::arg("nev") = 2, py::arg("dim") = 16, py::arg("tol") = 0.0,
+            py::arg("max_restarts") = 64, py::arg("prepare") = -1,
+            "(values, residuals, info) of the `nev` lowest eigenpairs of H from the current state: "
+            "thick-restart Lanczos with full re-orthogonalisation on a basis of at most `dim` vectors, "
+            "restarted up to `max_restarts` times until every residual is <= max(tol, rounding level). "
+            "info holds converged, restarts, applies and the per-cycle history_values / "
+            "history_residuals, shape (restarts + 1, nev), NaN-padded. prepare=i leaves Ritz vector i "
+            "in the simulator at unit norm; prepare=-1 leaves the state bit-identical. A single start "
+            "vector finds each eigenspace once: a degenerate level appears once, and a start vector "
+            "inside a symmetry sector finds only that sector's levels. The dense engines need dim + 1 "
+            "states of memory, one more with max_restarts > 0")
         .def("prob_bits_all",
             [](QI& q, std::vector<bitLenInt> bits) {
                 py::array_t<double> out((py::ssize_t)pow2((bitLenInt)bits.size()));
@@ -1271,6 +1302,7 @@ PYBIND11_MODULE(_qrack, m)
         "exp(-i time T) e_1 for the symmetric tridiagonal T with diagonal alpha and off-diagonal "
         "beta[:len(alpha) - 1] (lanczos_tridiagonal's output can be passed as it is)");
     m.attr("KRYLOV_MAX_DIM") = (int)KRYLOV_MAX_DIM;
+    m.attr("KRYLOV_EIG_MAX_NEV") = (int)KRYLOV_EIG_MAX_NEV;
     // basis vectors one combine launch of the HIP engine adds to the state
     m.attr("KRYLOV_COMBINE_MAX_VECTORS") = (int)KRYLOV_COMBINE_MAX_VECTORS;
     m.attr("MTRXN_MAX") = (int)QA_MTRXN_MAX;

@@ -739,6 +739,32 @@ double qrack_lanczos_ground_state(quid sid, uint64_t nTerms, const double* coeff
     });
 }
 
+uint64_t qrack_lanczos_lowest_states(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, int nev, int dim, double tol,
+    int maxRestarts, int prepare, double* values, double* residuals, int* converged, int* restarts,
+    int* applies, double* historyValues, double* historyResiduals)
+{
+    uint64_t m = 0;
+    *converged = *restarts = *applies = 0;
+    guarded(sid, [&](SimSlot& s) {
+        const std::vector<PauliTerm> terms
+            = flatPauliTerms(nTerms, coeffs, termLens, qs, paulis, "qrack_lanczos_lowest_states");
+        KrylovEigenResult r;
+        FOR_SIM(s, r = q.LanczosLowestStates(terms, nev, dim, tol, maxRestarts, prepare));
+        std::copy(r.values.begin(), r.values.end(), values);
+        std::copy(r.residuals.begin(), r.residuals.end(), residuals);
+        *converged = r.converged ? 1 : 0;
+        *restarts = r.restarts;
+        *applies = r.applies;
+        if (historyValues) std::copy(r.historyValues.begin(), r.historyValues.end(), historyValues);
+        if (historyResiduals) {
+            std::copy(r.historyResiduals.begin(), r.historyResiduals.end(), historyResiduals);
+        }
+        m = r.values.size();
+    });
+    return m;
+}
+
 void qrack_qft(quid sid, uint64_t start, uint64_t length)
 {
     guarded(sid, [&](SimSlot& s) { FOR_SIM(s, q.QFT((bitLenInt)start, (bitLenInt)length)); });

@@ -5356,6 +5356,194 @@ void launchKrylovCombine(cplx<R>* state, bitCapInt nAmps, const KrylovCombineArg
         (k_krylov_combine<R>), dim3(gridForPairs(nItems)), dim3(QA_BLOCK), 0, stream, state, a, nItems);
 }
 
+// ---- Krylov: block orthogonalisation, basis rotation --------------------------------
+//
+// One launch of k_krylov_orth handles a chunk of up to 16 basis vectors u_i
+// (krylov.hpp, LanczosLowestStates): with coef it first takes
+//   w <- w - sum_i (scale_i coef_i) u_i,   coef_i = (coef[2i], coef[2i + 1])
+// read from device memory, the folded result of an earlier launch, so that no
+// coefficient visits the host between launches; then it forms <u_i|w> for
+// every i and ||w||^2 of that w. Every u_i is loaded once and kept in
+// registers between the two uses. Products are formed in R, sums are double.
+// All per-vector arrays are indexed by fully unrolled loops under wave-uniform
+// guards, so they live in registers. Each block leaves its 33 sums in
+// partials[q * gridDim.x + block]; k_krylov_orth_fold adds them in a fixed
+// order, one wave per sum. No atomics.
+
+static inline int gridForOrth(bitCapInt nItems)
+{
+    int grid = gridForPairs(nItems);
+    return grid > KRYLOV_ORTH_MAX_BLOCKS ? KRYLOV_ORTH_MAX_BLOCKS : grid;
+}
+
+int krylovOrthGrid(bitCapInt nItems) { return gridForOrth(nItems); }
+
+// The launch bounds lift the 128-register limit of a 1024-thread block (16
+// vectors and 33 double sums per thread need more, and would spill under it)
+// and keep two waves on a SIMD.
+template <typename R, bool STORE>
+__global__ void __launch_bounds__(QA_BLOCK, 2) k_krylov_orth(
+    cplx<R>* w, KrylovOrthArgs<R> a, const double* coef, bitCapInt nItems, double* partials)
+{
+    constexpr int N = KRYLOV_ORTH_MAX_VECTORS;
+    using V = typename std::conditional<sizeof(R) == 4, float4, double2>::type;
+    double accRe[N], accIm[N];
+    R cr[N], ci[N];
+    double nrm = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        accRe[i] = 0;
+        accIm[i] = 0;
+        cr[i] = 0;
+        ci[i] = 0;
+        if (coef && i < a.n) {
+            cr[i] = (R)(a.scale[i] * coef[2 * i]);
+            ci[i] = (R)(a.scale[i] * coef[2 * i + 1]);
+        }
+    }
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        V W = reinterpret_cast<V*>(w)[v];
+        V U[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (i < a.n) U[i] = reinterpret_cast<const V*>(a.u[i])[v];
+        }
+        if (coef) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                if (i < a.n) {
+                    W.x -= cr[i] * U[i].x - ci[i] * U[i].y;
+                    W.y -= cr[i] * U[i].y + ci[i] * U[i].x;
+                    if constexpr (sizeof(R) == 4) {
+                        W.z -= cr[i] * U[i].z - ci[i] * U[i].w;
+                        W.w -= cr[i] * U[i].w + ci[i] * U[i].z;
+                    }
+                }
+            }
+            if constexpr (STORE) reinterpret_cast<V*>(w)[v] = W;
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (i < a.n) {
+                if constexpr (sizeof(R) == 4) {
+                    accRe[i] += (double)(U[i].x * W.x + U[i].y * W.y) + (double)(U[i].z * W.z + U[i].w * W.w);
+                    accIm[i] += (double)(U[i].x * W.y - U[i].y * W.x) + (double)(U[i].z * W.w - U[i].w * W.z);
+                } else {
+                    accRe[i] += U[i].x * W.x + U[i].y * W.y;
+                    accIm[i] += U[i].x * W.y - U[i].y * W.x;
+                }
+            }
+        }
+        if constexpr (sizeof(R) == 4) {
+            nrm += (double)(W.x * W.x + W.y * W.y) + (double)(W.z * W.z + W.w * W.w);
+        } else {
+            nrm += W.x * W.x + W.y * W.y;
+        }
+    }
+    // block sums of all 33 values behind one barrier: a row of LDS per value
+    constexpr int Q = KRYLOV_ORTH_RESULTS;
+    __shared__ double waveSums[Q][QA_BLOCK / 64];
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const double re = waveReduceSum(accRe[i]);
+        const double im = waveReduceSum(accIm[i]);
+        if (lane == 0) {
+            waveSums[2 * i][wid] = re;
+            waveSums[2 * i + 1][wid] = im;
+        }
+    }
+    nrm = waveReduceSum(nrm);
+    if (lane == 0) waveSums[Q - 1][wid] = nrm;
+    __syncthreads();
+    if (threadIdx.x < Q) {
+        double t = 0;
+        for (int k = 0; k < QA_BLOCK / 64; ++k) t += waveSums[threadIdx.x][k];
+        partials[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+// result[q] = sum over the blocks of partials[q * n + block], wave q % 4 of
+// the one block, lanes striding the blocks: a fixed order
+__global__ void k_krylov_orth_fold(const double* partials, int n, double* result)
+{
+    const int lane = threadIdx.x & 63;
+    for (int q = threadIdx.x >> 6; q < KRYLOV_ORTH_RESULTS; q += QA_BLOCK / 64) {
+        double s = 0;
+        for (int b = lane; b < n; b += 64) s += partials[(size_t)q * n + b];
+        s = waveReduceSum(s);
+        if (lane == 0) result[q] = s;
+    }
+}
+
+template <typename R>
+void launchKrylovOrth(cplx<R>* w, bitCapInt nAmps, const KrylovOrthArgs<R>& a, const double* coefDev,
+    bool store, double* partialsDev, double* resultDev, hipStream_t stream)
+{
+    const bitCapInt nItems = (sizeof(R) == 4) ? (nAmps >> 1u) : nAmps;
+    const int grid = gridForOrth(nItems);
+    const dim3 g(grid), b(QA_BLOCK);
+    if (store && coefDev) {
+        hipLaunchKernelGGL((k_krylov_orth<R, true>), g, b, 0, stream, w, a, coefDev, nItems, partialsDev);
+    } else {
+        hipLaunchKernelGGL((k_krylov_orth<R, false>), g, b, 0, stream, w, a, coefDev, nItems, partialsDev);
+    }
+    hipLaunchKernelGGL(k_krylov_orth_fold, dim3(1), dim3(QA_BLOCK), 0, stream, partialsDev, grid, resultDev);
+}
+
+// The restart: out_i = sum_r m[r * 16 + i] in_r for i < kp, r < k, with the
+// real matrix (rows padded to 16, the basis's scales folded in by the host)
+// read wave-uniformly from device memory. A thread reads its element of every
+// input before it writes its element of the outputs, so an output may be one
+// of the inputs' buffers. The kp accumulators stay in registers.
+template <typename R> __global__ void k_krylov_rotate(KrylovRotateArgs<R> a, const R* m, bitCapInt nItems)
+{
+    constexpr int N = KRYLOV_COMBINE_MAX_VECTORS;
+    using V = typename std::conditional<sizeof(R) == 4, float4, double2>::type;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        V acc[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if constexpr (sizeof(R) == 4) {
+                acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                acc[i] = make_double2(0.0, 0.0);
+            }
+        }
+        for (int r = 0; r < a.k; ++r) {
+            const V U = reinterpret_cast<const V*>(a.in[r])[v];
+            const R* row = m + r * N;
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                if (i < a.kp) {
+                    const R c = row[i];
+                    acc[i].x += c * U.x;
+                    acc[i].y += c * U.y;
+                    if constexpr (sizeof(R) == 4) {
+                        acc[i].z += c * U.z;
+                        acc[i].w += c * U.w;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (i < a.kp) reinterpret_cast<V*>(a.out[i])[v] = acc[i];
+        }
+    }
+}
+
+template <typename R>
+void launchKrylovRotate(const KrylovRotateArgs<R>& a, const R* mDev, bitCapInt nAmps, hipStream_t stream)
+{
+    const bitCapInt nItems = (sizeof(R) == 4) ? (nAmps >> 1u) : nAmps;
+    hipLaunchKernelGGL(
+        (k_krylov_rotate<R>), dim3(gridForPairs(nItems)), dim3(QA_BLOCK), 0, stream, a, mDev, nItems);
+}
+
 // ---- reduced density matrices -----------------------------------------------------
 //
 // rho[a,b] = sum_e psi[e,a] conj(psi[e,b]) over the kept qubits in ascending
@@ -5715,6 +5903,9 @@ void launchRdmTile(const cplx<R>* sv, int kt, const RdmTileArgs& a, double* part
         double, bool, double*, double*, hipStream_t);                                               \
     template void launchKrylovCombine<R>(                                                           \
         cplx<R>*, bitCapInt, const KrylovCombineArgs<R>&, hipStream_t);                             \
+    template void launchKrylovOrth<R>(cplx<R>*, bitCapInt, const KrylovOrthArgs<R>&, const double*, \
+        bool, double*, double*, hipStream_t);                                                       \
+    template void launchKrylovRotate<R>(const KrylovRotateArgs<R>&, const R*, bitCapInt, hipStream_t); \
     template void launchRdmReg<R>(                                                                  \
         const cplx<R>*, int, bool, const RdmRegArgs&, double*, double*, hipStream_t);               \
     template void launchRdmTile<R>(                                                                 \

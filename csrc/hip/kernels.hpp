@@ -252,6 +252,43 @@ template <typename R> struct KrylovCombineArgs {
 template <typename R>
 void launchKrylovCombine(cplx<R>* state, bitCapInt nAmps, const KrylovCombineArgs<R>& a, hipStream_t stream);
 
+// Orthogonalisation of LanczosLowestStates (krylov.hpp) against one chunk of
+// n <= KRYLOV_ORTH_MAX_VECTORS unnormalised basis vectors. With coefDev:
+// w <- w - sum_i (scale[i] * (coefDev[2i] + i coefDev[2i + 1])) u[i] first
+// (stored only with `store`). Then resultDev[2i], resultDev[2i + 1] <- (re, im)
+// of <u[i]|w> and resultDev[32] <- ||w||^2, of that w. coefDev is the
+// resultDev of an earlier launch on the stream, or null: the read-only
+// inner-product pass. partialsDev holds KRYLOV_ORTH_RESULTS *
+// krylovOrthGrid(items) doubles, items = nAmps (fp64) or nAmps / 2 (fp32);
+// the grid obeys the QRACK_GPU_BLOCKS cap.
+constexpr int KRYLOV_ORTH_RESULTS = 2 * KRYLOV_ORTH_MAX_VECTORS + 1;
+// Two blocks per CU are resident whatever the register count turns out to be,
+// and 17 loads of 16 B in flight per thread keep HBM busy from there; the cap
+// also lets the partials fit the engine's reduction buffer.
+constexpr int KRYLOV_ORTH_MAX_BLOCKS = 512;
+static_assert(KRYLOV_ORTH_RESULTS * KRYLOV_ORTH_MAX_BLOCKS <= 2 * QA_REDUCE_MAX_BLOCKS,
+    "the orth partials live in the reduction partials buffer");
+template <typename R> struct KrylovOrthArgs {
+    const cplx<R>* u[KRYLOV_ORTH_MAX_VECTORS];
+    double scale[KRYLOV_ORTH_MAX_VECTORS];
+    int n;
+};
+int krylovOrthGrid(bitCapInt nItems);
+template <typename R>
+void launchKrylovOrth(cplx<R>* w, bitCapInt nAmps, const KrylovOrthArgs<R>& a, const double* coefDev,
+    bool store, double* partialsDev, double* resultDev, hipStream_t stream);
+
+// The restart's rotation: out[i] <- sum_r mDev[r * 16 + i] in[r], i < kp,
+// r < k, a real matrix in R with rows padded to KRYLOV_COMBINE_MAX_VECTORS.
+// Elementwise across the buffers: an out[i] may be one of the in[r].
+template <typename R> struct KrylovRotateArgs {
+    const cplx<R>* in[KRYLOV_MAX_DIM];
+    cplx<R>* out[KRYLOV_COMBINE_MAX_VECTORS];
+    int k, kp;
+};
+template <typename R>
+void launchKrylovRotate(const KrylovRotateArgs<R>& a, const R* mDev, bitCapInt nAmps, hipStream_t stream);
+
 template <typename R>
 void launchApply2x2(cplx<R>* sv, const GateArgs<R>& a, hipStream_t stream);
 

@@ -2080,6 +2080,152 @@ std::pair<double, double> QEngineHIP<R>::LanczosGroundState(const std::vector<Pa
     return { lambda, run.beta[k - 1u] * std::abs(y[k - 1u]) };
 }
 
+template <typename R>
+KrylovEigenResult QEngineHIP<R>::LanczosLowestStates(
+    const std::vector<PauliTerm>& terms, int nev, int dim, double tol, int maxRestarts, int prepare)
+{
+    validateKrylovEigenArgs(nev, dim, tol, maxRestarts, prepare);
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "LanczosLowestStates");
+    QA_HIP_CHECK(hipSetDevice(deviceId));
+    // the basis and w, all up front: a refusal leaves the state untouched. A
+    // cycle after a restart has no state among its dim vectors, hence one more
+    KrylovBuffers bufs(this);
+    bufs.take((size_t)dim + (maxRestarts > 0 ? 1u : 0u));
+    const std::vector<PauliArgs> launches = pauliSumLaunches(c, maxQPower);
+    const size_t L = launches.size();
+    ReduceArgs ra{};
+    ra.maxI = maxQPower;
+    const double nrm = reduceSum((int)ReduceOp::NORM_ALL, ra);
+    if (!(nrm > 0)) throw QrackError("LanczosLowestStates: the state has zero norm");
+    const double theta = krylovTheta(L, (double)std::numeric_limits<R>::epsilon(), pauliSumAbsWeights(c));
+    // 33 results for every orth launch of a step, then the slots where the
+    // apply launches leave their shares of <u|H u>, which nobody reads. The
+    // block partials of a launch go through dPartials, in stream order.
+    constexpr size_t Q = (size_t)KRYLOV_ORTH_RESULTS;
+    const size_t maxLaunches = (size_t)krylovOrthLaunches(dim);
+    double* dOrthRes = pairResults((Q * maxLaunches + L + 1u) / 2u);
+    double* dSlots = dOrthRes + Q * maxLaunches;
+    double* dOrthPartials = dPartials;
+    std::vector<double> hRes(Q * maxLaunches);
+
+    const cplx<R>* sv = rState();
+    std::vector<const cplx<R>*> basis(1, sv);
+    std::vector<cplx<R>*> spare(bufs.p.rbegin(), bufs.p.rend());
+    cplx<R>* w = nullptr;
+    constexpr int CAP = KRYLOV_ORTH_MAX_VECTORS;
+
+    auto step = [&](int j, const std::vector<double>& scale) {
+        w = spare.back();
+        const double s = scale[(size_t)(j - 1)];
+        for (size_t k = 0; k < L; ++k) {
+            PauliArgs a = launches[k];
+            for (int t = 0; t < a.nTerms; ++t) a.w[t] *= s;
+            HipProfScope prof("krylov_apply", stream);
+            launchKrylovApply<R>(
+                basis[(size_t)(j - 1)], nullptr, w, a, s * c.identity, 0.0, k == 0u, dPartials, dSlots + k, stream);
+        }
+        auto chunk = [&](int g0) {
+            KrylovOrthArgs<R> a{};
+            a.n = std::min(CAP, j - g0);
+            for (int i = 0; i < a.n; ++i) {
+                a.u[i] = basis[(size_t)(g0 + i)];
+                a.scale[i] = scale[(size_t)(g0 + i)] * scale[(size_t)(g0 + i)];
+            }
+            return a;
+        };
+        size_t nLaunch = 0;
+        auto orth = [&](const KrylovOrthArgs<R>& a, const double* coef) {
+            double* res = dOrthRes + Q * nLaunch++;
+            HipProfScope prof("krylov_orth", stream);
+            launchKrylovOrth<R>(w, maxQPower, a, coef, coef != nullptr, dOrthPartials, res, stream);
+            return res;
+        };
+        KrylovOrthStep r;
+        r.h.assign((size_t)j, cplx<double>(0.0, 0.0));
+        // which launch's results hold c_i of (round, chunk)
+        std::vector<std::pair<size_t, int>> ips;
+        if (j <= CAP) {
+            const KrylovOrthArgs<R> a = chunk(0);
+            const double* r0 = orth(a, nullptr);
+            const double* r1 = orth(a, r0);
+            orth(a, r1);
+            ips = { { 0u, 0 }, { 1u, 0 } };
+        } else {
+            for (int round = 0; round < 2; ++round) {
+                for (int g0 = 0; g0 < j; g0 += CAP) {
+                    const KrylovOrthArgs<R> a = chunk(g0);
+                    ips.push_back({ nLaunch, g0 });
+                    orth(a, orth(a, nullptr));
+                }
+            }
+        }
+        QA_HIP_CHECK(hipMemcpyAsync(
+            hRes.data(), dOrthRes, Q * nLaunch * sizeof(double), hipMemcpyDeviceToHost, stream));
+        Finish(); // the host needs beta for the next scale
+        for (const std::pair<size_t, int>& ip : ips) {
+            const double* res = hRes.data() + Q * ip.first;
+            const int n = std::min(CAP, j - ip.second);
+            for (int i = 0; i < n; ++i) {
+                const double si = scale[(size_t)(ip.second + i)];
+                cplx<double>& h = r.h[(size_t)(ip.second + i)];
+                h = h + cplx<double>(si * res[2 * i], si * res[2 * i + 1]);
+            }
+        }
+        r.norm2 = hRes[Q * (nLaunch - 1u) + Q - 1u];
+        return r;
+    };
+    auto accept = [&]() {
+        basis.push_back(w);
+        spare.pop_back();
+    };
+    auto rotate = [&](int k, int kp, const std::vector<double>& m) {
+        // the outputs take the place of inputs, never the state's
+        std::vector<cplx<R>*> own;
+        for (const cplx<R>* b : basis) {
+            if (b != sv) own.push_back(const_cast<cplx<R>*>(b));
+        }
+        KrylovRotateArgs<R> a{};
+        a.k = k;
+        a.kp = kp;
+        for (int r = 0; r < k; ++r) a.in[r] = basis[(size_t)r];
+        for (int i = 0; i < kp; ++i) a.out[i] = own[(size_t)i];
+        constexpr size_t N = (size_t)KRYLOV_COMBINE_MAX_VECTORS;
+        QA_HIP_CHECK(hipStreamSynchronize(stream)); // hAux_ and dAux_ are free again
+        hAux_.assign(sizeof(R) * (size_t)k * N, 0);
+        R* hm = reinterpret_cast<R*>(hAux_.data());
+        for (int r = 0; r < k; ++r) {
+            for (int i = 0; i < kp; ++i) hm[(size_t)r * N + (size_t)i] = (R)m[(size_t)r * (size_t)kp + (size_t)i];
+        }
+        const R* dm = reinterpret_cast<const R*>(uploadAux(hAux_.size()));
+        {
+            HipProfScope prof("krylov_rotate", stream);
+            launchKrylovRotate<R>(a, dm, maxQPower, stream);
+        }
+        spare.pop_back(); // w, which becomes u~_(kp+1)
+        for (size_t i = (size_t)kp; i < own.size(); ++i) spare.push_back(own[i]);
+        basis.assign(own.begin(), own.begin() + kp);
+        basis.push_back(w);
+    };
+    const KrylovEigenRun run = krylovEigenDrive(
+        nev, dim, tol, maxRestarts, prepare, std::sqrt(nrm), theta, step, accept, rotate);
+    if (prepare >= 0) {
+        if (run.prepareCoef.empty()) {
+            throw QrackError("LanczosLowestStates: the run ended with fewer than prepare + 1 pairs");
+        }
+        // krylovCombine's form: the state's own coefficient first
+        const bool first = basis[0] == sv;
+        std::vector<cplx<double>> coef(1, cplx<double>(first ? run.prepareCoef[0] : 0.0, 0.0));
+        std::vector<cplx<R>*> src;
+        for (size_t r = first ? 1u : 0u; r < basis.size(); ++r) {
+            coef.push_back(cplx<double>(run.prepareCoef[r], 0.0));
+            src.push_back(const_cast<cplx<R>*>(basis[r]));
+        }
+        krylovCombine(coef, src);
+        runningNorm = (R)1;
+    }
+    return run.result;
+}
+
 template <typename R> std::pair<double, bitCapInt> QEngineHIP<R>::argMax()
 {
     QA_HIP_CHECK(hipSetDevice(deviceId));

@@ -252,6 +252,19 @@ public:
         const std::vector<PauliTerm>& terms, double time, int dim = 16, int steps = 1) override;
     std::pair<double, double> LanczosGroundState(
         const std::vector<PauliTerm>& terms, int dim = 32, bool prepare = false) override;
+    // krylovEigenDrive (krylov.hpp). A step at basis size j is L apply
+    // launches (the first writes w without reading it), then the block
+    // orthogonalisation: krylovOrthLaunches(j) launches of k_krylov_orth, whose
+    // coefficients stay on the device, (3j + 5) state sizes for j <= 16; then
+    // one copy of h and beta^2 and one host sync. A restart is one in-place
+    // k_krylov_rotate, (k + kp) state sizes, and a pointer swap. Launches of a
+    // call: applies * L krylov_apply, the sum of krylovOrthLaunches(j) over
+    // its steps krylov_orth, restarts krylov_rotate, and krylov_combine only
+    // with prepare >= 0. dim buffers besides the state, dim + 1 with
+    // maxRestarts > 0 (a later cycle's dim vectors and its w are all the
+    // call's own), taken up front.
+    KrylovEigenResult LanczosLowestStates(const std::vector<PauliTerm>& terms, int nev = 2, int dim = 16,
+        double tol = 0.0, int maxRestarts = 64, int prepare = -1) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;

@@ -1303,6 +1303,130 @@ std::pair<double, double> QEngineCPU<R>::LanczosGroundState(const std::vector<Pa
     return { lambda, run.beta[k - 1u] * std::abs(y[k - 1u]) };
 }
 
+template <typename R>
+KrylovEigenResult QEngineCPU<R>::LanczosLowestStates(
+    const std::vector<PauliTerm>& terms, int nev, int dim, double tol, int maxRestarts, int prepare)
+{
+    validateKrylovEigenArgs(nev, dim, tol, maxRestarts, prepare);
+    const PauliCanonSum c = canonicalizePauliSum(terms, qubitCount, "LanczosLowestStates");
+    cplx<R>* sv = stateVec.data();
+    double nrm = 0, comp = 0;
+    this->par_sum2(maxQPower, [=](const bitCapInt& i, double& sum, double& cmp) {
+        kahanAdd(sum, cmp, (double)(sv[i].re * sv[i].re + sv[i].im * sv[i].im));
+    }, nrm, comp);
+    nrm -= comp;
+    if (!(nrm > 0)) throw QrackError("LanczosLowestStates: the state has zero norm");
+    const double theta = krylovTheta(
+        pauliSumLaunchCount(c), (double)std::numeric_limits<R>::epsilon(), pauliSumAbsWeights(c));
+    // the basis and w; a later cycle has no state among its vectors
+    std::vector<std::vector<cplx<R>>> bufs(
+        (size_t)dim + (maxRestarts > 0 ? 1u : 0u), std::vector<cplx<R>>(maxQPower));
+    std::vector<const cplx<R>*> basis(1, sv);
+    std::vector<cplx<R>*> spare;
+    for (size_t b = bufs.size(); b-- > 0u;) spare.push_back(bufs[b].data());
+    cplx<R>* w = nullptr;
+    constexpr int CAP = KRYLOV_ORTH_MAX_VECTORS;
+
+    auto step = [&](int j, const std::vector<double>& scale) {
+        w = spare.back();
+        const double s = scale[(size_t)(j - 1)];
+        PauliCanonSum cs = c;
+        cs.identity *= s;
+        for (PauliGroup& g : cs.groups) {
+            for (PauliCanonTerm& t : g.re) t.w *= s;
+            for (PauliCanonTerm& t : g.im) t.w *= s;
+        }
+        pauliApplyRun(cs, basis[(size_t)(j - 1)], w);
+        KrylovOrthStep r;
+        r.h.assign((size_t)j, cplx<double>(0.0, 0.0));
+        cplx<R>* wp = w;
+        for (int round = 0; round < 2; ++round) {
+            for (int g0 = 0; g0 < j; g0 += CAP) {
+                const int n = std::min(CAP, j - g0);
+                cplx<R> cf[CAP];
+                const cplx<R>* us[CAP];
+                for (int i = 0; i < n; ++i) {
+                    const cplx<R>* u = us[i] = basis[(size_t)(g0 + i)];
+                    double re = 0, reC = 0, im = 0, imC = 0;
+                    this->par_sum2(maxQPower, [=](const bitCapInt& x, double& sum, double& cmp) {
+                        kahanAdd(sum, cmp, (double)(u[x].re * wp[x].re + u[x].im * wp[x].im));
+                    }, re, reC);
+                    this->par_sum2(maxQPower, [=](const bitCapInt& x, double& sum, double& cmp) {
+                        kahanAdd(sum, cmp, (double)(u[x].re * wp[x].im - u[x].im * wp[x].re));
+                    }, im, imC);
+                    re -= reC;
+                    im -= imC;
+                    const double si = scale[(size_t)(g0 + i)];
+                    cf[i] = cplx<R>((R)(si * si * re), (R)(si * si * im));
+                    r.h[(size_t)(g0 + i)] = r.h[(size_t)(g0 + i)] + cplx<double>(si * re, si * im);
+                }
+                std::vector<cplx<R>> cfv(cf, cf + n);
+                std::vector<const cplx<R>*> usv(us, us + n);
+                const cplx<R>* cfp = cfv.data();
+                const cplx<R>* const* usp = usv.data();
+                this->par_for(0, maxQPower, [=](const bitCapInt& x, unsigned) {
+                    cplx<R> acc = wp[x];
+                    for (int i = 0; i < n; ++i) acc = acc - cfp[i] * usp[i][x];
+                    wp[x] = acc;
+                });
+            }
+        }
+        double n2 = 0, n2C = 0;
+        this->par_sum2(maxQPower, [=](const bitCapInt& x, double& sum, double& cmp) {
+            kahanAdd(sum, cmp, (double)(wp[x].re * wp[x].re + wp[x].im * wp[x].im));
+        }, n2, n2C);
+        r.norm2 = n2 - n2C;
+        return r;
+    };
+    auto accept = [&]() {
+        basis.push_back(w);
+        spare.pop_back();
+    };
+    auto rotate = [&](int k, int kp, const std::vector<double>& m) {
+        // elementwise across the arrays, so the outputs may take the place of
+        // inputs; never the state's, which prepare = -1 keeps
+        std::vector<cplx<R>*> own;
+        for (const cplx<R>* b : basis) {
+            if (b != sv) own.push_back(const_cast<cplx<R>*>(b));
+        }
+        std::vector<R> mr(m.begin(), m.end());
+        const R* mp = mr.data();
+        const cplx<R>* const* in = basis.data();
+        cplx<R>* const* outp = own.data();
+        this->par_for(0, maxQPower, [=](const bitCapInt& x, unsigned) {
+            cplx<R> acc[KRYLOV_COMBINE_MAX_VECTORS];
+            for (int i = 0; i < kp; ++i) acc[i] = cplx<R>((R)0, (R)0);
+            for (int r = 0; r < k; ++r) {
+                const cplx<R> a = in[r][x];
+                for (int i = 0; i < kp; ++i) acc[i] = acc[i] + mp[(size_t)r * (size_t)kp + (size_t)i] * a;
+            }
+            for (int i = 0; i < kp; ++i) outp[i][x] = acc[i];
+        });
+        spare.pop_back(); // w, which becomes u~_(kp+1)
+        for (size_t i = (size_t)kp; i < own.size(); ++i) spare.push_back(own[i]);
+        basis.assign(own.begin(), own.begin() + kp);
+        basis.push_back(w);
+    };
+    const KrylovEigenRun run = krylovEigenDrive(
+        nev, dim, tol, maxRestarts, prepare, std::sqrt(nrm), theta, step, accept, rotate);
+    if (prepare >= 0) {
+        if (run.prepareCoef.empty()) {
+            throw QrackError("LanczosLowestStates: the run ended with fewer than prepare + 1 pairs");
+        }
+        std::vector<R> cf(run.prepareCoef.begin(), run.prepareCoef.end());
+        const R* cfp = cf.data();
+        const cplx<R>* const* in = basis.data();
+        const int k = run.k;
+        this->par_for(0, maxQPower, [=](const bitCapInt& x, unsigned) {
+            cplx<R> acc((R)0, (R)0);
+            for (int r = 0; r < k; ++r) acc = acc + cfp[r] * in[r][x];
+            sv[x] = acc;
+        });
+        runningNorm = (R)1;
+    }
+    return run.result;
+}
+
 template <typename R> bool QEngineCPU<R>::ForceMParity(bitCapInt mask, bool result, bool doForce)
 {
     if (!mask) return false;

@@ -126,6 +126,11 @@ public:
         const std::vector<PauliTerm>& terms, double time, int dim = 16, int steps = 1) override;
     std::pair<double, double> LanczosGroundState(
         const std::vector<PauliTerm>& terms, int dim = 32, bool prepare = false) override;
+    // krylovEigenDrive around plain sweeps: H v_j through pauliApplyRun on
+    // scaled weights, then per chunk one Kahan sum per inner product and one
+    // update sweep. dim amplitude arrays, dim + 1 when maxRestarts > 0.
+    KrylovEigenResult LanczosLowestStates(const std::vector<PauliTerm>& terms, int nev = 2, int dim = 16,
+        double tol = 0.0, int maxRestarts = 64, int prepare = -1) override;
 
     // ---- structural ----
     using QInterface<R>::Compose;

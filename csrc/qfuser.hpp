@@ -252,6 +252,12 @@ public:
         FlushAll();
         return inner->LanczosGroundState(t, dim, prepare);
     }
+    KrylovEigenResult LanczosLowestStates(const std::vector<PauliTerm>& t, int nev = 2, int dim = 16,
+        double tol = 0.0, int maxRestarts = 64, int prepare = -1) override
+    {
+        FlushAll();
+        return inner->LanczosLowestStates(t, nev, dim, tol, maxRestarts, prepare);
+    }
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override { FlushAll(); return inner->TrySeparate(q); }

@@ -894,6 +894,17 @@ std::pair<double, double> QInterface<R>::LanczosGroundState(
     return r;
 }
 
+template <typename R>
+KrylovEigenResult QInterface<R>::LanczosLowestStates(
+    const std::vector<PauliTerm>& terms, int nev, int dim, double tol, int maxRestarts, int prepare)
+{
+    validateKrylovEigenArgs(nev, dim, tol, maxRestarts, prepare);
+    auto engine = krylovHostEngine(*this, terms, dim, 1, "LanczosLowestStates");
+    const KrylovEigenResult r = engine->LanczosLowestStates(terms, nev, dim, tol, maxRestarts, prepare);
+    if (prepare >= 0) krylovCopyBack(*this, *engine);
+    return r;
+}
+
 // ---- ALU defaults ----------------------------------------------------------
 
 template <typename R> static void aluThrow()

@@ -57,6 +57,21 @@ inline void validateKrylovArgs(int dim, int steps, const char* what)
     if (steps < 1) throw QrackError(std::string(what) + ": steps must be at least 1");
 }
 
+// ... and of LanczosLowestStates
+inline void validateKrylovEigenArgs(int nev, int dim, double tol, int maxRestarts, int prepare)
+{
+    const std::string what = "LanczosLowestStates: ";
+    if (nev < 1 || nev > KRYLOV_EIG_MAX_NEV) {
+        throw QrackError(what + "need 1 <= nev <= " + std::to_string(KRYLOV_EIG_MAX_NEV));
+    }
+    if (dim < nev + 2 || dim > KRYLOV_MAX_DIM) {
+        throw QrackError(what + "need nev + 2 <= dim <= " + std::to_string(KRYLOV_MAX_DIM));
+    }
+    if (!(tol >= 0)) throw QrackError(what + "tol must not be negative");
+    if (maxRestarts < 0) throw QrackError(what + "max_restarts must not be negative");
+    if (prepare < -1 || prepare >= nev) throw QrackError(what + "need -1 <= prepare < nev");
+}
+
 // most qubits a reduced density matrix may keep (a 4096 x 4096 result)
 constexpr int QA_RDM_MAX_QUBITS = 12;
 
@@ -982,6 +997,19 @@ public:
     // a plain restarted Lanczos; without it the state is bit-identical.
     virtual std::pair<double, double> LanczosGroundState(
         const std::vector<PauliTerm>& terms, int dim = 32, bool prepare = false);
+    // The nev lowest eigenpairs of H from the current state: thick-restart
+    // Lanczos with full re-orthogonalisation (krylov.hpp has the definition),
+    // a basis of at most dim vectors restarted up to maxRestarts times until
+    // every wanted residual is <= max(tol, theta). prepare = i leaves Ritz
+    // vector i of the final cycle in the simulator at unit norm (refused when
+    // the run produced fewer pairs), prepare = -1 leaves the state
+    // bit-identical. A single start vector finds each eigenspace once: a
+    // degenerate level appears once, and a start vector inside a symmetry
+    // sector finds only that sector's levels. Refusals are QrackErrors prefixed
+    // "LanczosLowestStates: ". The dense engines need dim + 1 states of memory,
+    // and one more when maxRestarts > 0. Default lowering: as above.
+    virtual KrylovEigenResult LanczosLowestStates(const std::vector<PauliTerm>& terms, int nev = 2,
+        int dim = 16, double tol = 0.0, int maxRestarts = 64, int prepare = -1);
     // product observable squares to identity: Var = 1 - E^2
     double PauliProductVariance(const std::vector<bitLenInt>& bits, const std::vector<Pauli>& paulis)
     {

@@ -76,6 +76,13 @@ public:
         if (prepare) throw QrackError("LanczosGroundState(prepare): not defined under gate noise");
         return inner->LanczosGroundState(t, dim, false);
     }
+    // ... and so is the read-only LanczosLowestStates
+    KrylovEigenResult LanczosLowestStates(const std::vector<PauliTerm>& t, int nev = 2, int dim = 16,
+        double tol = 0.0, int maxRestarts = 64, int prepare = -1) override
+    {
+        if (prepare >= 0) throw QrackError("LanczosLowestStates(prepare): not defined under gate noise");
+        return inner->LanczosLowestStates(t, nev, dim, tol, maxRestarts, -1);
+    }
 
     void Mtrx(const cplx<R>* m, bitLenInt t) override
     {

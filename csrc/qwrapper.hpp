@@ -207,6 +207,11 @@ public:
     {
         return inner->LanczosGroundState(t, dim, prepare);
     }
+    KrylovEigenResult LanczosLowestStates(const std::vector<PauliTerm>& t, int nev = 2, int dim = 16,
+        double tol = 0.0, int maxRestarts = 64, int prepare = -1) override
+    {
+        return inner->LanczosLowestStates(t, nev, dim, tol, maxRestarts, prepare);
+    }
 
     // ---- separability ----
     bool TrySeparate(bitLenInt q) override { return inner->TrySeparate(q); }

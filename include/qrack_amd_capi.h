@@ -138,6 +138,18 @@ double qrack_krylov_evolve_pauli_sum(quid sid, uint64_t nTerms, const double* co
 double qrack_lanczos_ground_state(quid sid, uint64_t nTerms, const double* coeffs,
     const uint64_t* termLens, const uint64_t* qs, const int* paulis, int dim, int prepare,
     double* residual);
+/* The nev lowest eigenpairs by thick-restart Lanczos with full
+ * re-orthogonalisation: 1 <= nev <= 8, nev + 2 <= dim <= 64, tol >= 0,
+ * maxRestarts >= 0, -1 <= prepare < nev (-1: sid is left untouched; i: Ritz
+ * vector i is left in sid at unit norm). values and residuals have room for
+ * nev doubles; returns how many pairs they received. historyValues and
+ * historyResiduals have room for (maxRestarts + 1) * nev doubles each, or are
+ * NULL; (*restarts + 1) rows of nev are written, NaN-padded. The dense engines
+ * need dim + 1 states of memory, one more with maxRestarts > 0 */
+uint64_t qrack_lanczos_lowest_states(quid sid, uint64_t nTerms, const double* coeffs,
+    const uint64_t* termLens, const uint64_t* qs, const int* paulis, int nev, int dim, double tol,
+    int maxRestarts, int prepare, double* values, double* residuals, int* converged, int* restarts,
+    int* applies, double* historyValues, double* historyResiduals);
 
 /* QFT */
 void qrack_qft(quid sid, uint64_t start, uint64_t length);

@@ -31,6 +31,7 @@ from qrack_amd._qrack import (  # noqa: F401
     mtrx_n_plan,
     krylov_coefficients,
     KRYLOV_MAX_DIM,
+    KRYLOV_EIG_MAX_NEV,
     KRYLOV_COMBINE_MAX_VECTORS,
     MTRXN_MAX,
     RDM_MAX_QUBITS,
