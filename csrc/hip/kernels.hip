@@ -4098,16 +4098,167 @@ void launchPartProbs(const cplx<R>* sv, bitCapInt maxQPower, bitLenInt start, bi
     }
 }
 
-// ---- Pauli-sum expectation -------------------------------------------------------
+// ---- Pauli pair walk --------------------------------------------------------------
 //
-// <psi|P|psi> with P|i> = i^ny (-1)^popcount(i&z) |i^x>. For x != 0 the pair
-// (i, i^x) contributes 2 Re(w(i) conj(psi[i^x]) psi[i]) with
-// w(i) = sum_t c_t i^ny_t (-1)^popcount(i&z_t), so only the half-space with
-// the top bit of x clear is walked: every amplitude is loaded once and nothing
-// is stored. fp32 streams float4 (two amplitudes): i is even, i+1 shares the
-// vector, and the partner vector sits at i ^ (x & ~1) — with bit 0 of x set
-// its halves are swapped in registers. x == 1 pairs the two halves of one
-// vector. fp64 amplitudes are 16 B each already.
+// P|i> = i^ny (-1)^popcount(i&z) |i^x>. Every kernel from here to
+// k_krylov_finish walks the index pairs (i, j = i^x) of one group of terms that
+// share x, and only the half-space with the top bit of x clear: every amplitude
+// of every vector involved is loaded once and, where written, stored once by
+// exactly one thread. PairItem states the addressing; the kernels below are
+// arithmetic over its lanes.
+//
+// An item is one 16-byte access per stream: one amplitude in fp64, two in fp32.
+//   MODE 0  fp64: one pair per item, a = psi[i], b = psi[i^x].
+//   MODE 1  fp32, x != 1: two pairs per item. i is even and i + 1 shares the
+//           float4; the partner vector sits at i ^ (x & ~1), and with bit 0 of
+//           x set its halves are swapped in registers on load and swapped back
+//           before a store.
+//   MODE 2  fp32, x == 1: the pair is the two halves of one vector.
+//   MODE -1 x == 0 (the diagonal kernels): no partner, only the a lanes; two
+//           in fp32, one in fp64.
+// Lane l of a holds index i + l, lane l of b its partner (i + l) ^ x.
+template <typename R, int MODE> struct PairItem {
+    static constexpr bool F32 = sizeof(R) == 4;
+    static_assert(MODE == -1 || (MODE == 0) == !F32, "MODE 0 is fp64, MODE 1 and 2 are fp32");
+    static constexpr int L = (MODE == 1 || (MODE == -1 && F32)) ? 2 : 1;
+    static constexpr bool TWO = (L == 2);
+    using Vec = std::conditional_t<F32, float4, double2>;
+
+    bitCapInt i;      // amplitude index of lane 0 of a
+    bitCapInt ia, ib; // vector index of the a lanes and of the b lanes
+    bool swapped;     // the b vector holds lane 1 in its lower half
+
+    __device__ __forceinline__ PairItem(bitCapInt v, bitCapInt topPow, bitCapInt x)
+    {
+        if constexpr (MODE == 0) {
+            i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
+            ia = i;
+            ib = i ^ x;
+        } else if constexpr (MODE == 1) {
+            const bitCapInt j = v << 1u;
+            i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
+            ia = i >> 1u;
+            ib = (i ^ x) >> 1u;
+        } else {
+            i = F32 ? (v << 1u) : v;
+            ia = ib = v;
+        }
+        swapped = (MODE == 1) && (x & 1u) != 0;
+    }
+
+    // NT (nontemporal access) exists for the float4 streams only
+    template <bool NT> static __device__ __forceinline__ Vec ldv(const cplx<R>* p, bitCapInt k)
+    {
+        if constexpr (F32) return ld4<NT>(reinterpret_cast<const float4*>(p) + k);
+        else return reinterpret_cast<const double2*>(p)[k];
+    }
+    template <bool NT> static __device__ __forceinline__ void stv(cplx<R>* p, bitCapInt k, Vec V)
+    {
+        if constexpr (F32) st4<NT>(reinterpret_cast<float4*>(p) + k, V);
+        else reinterpret_cast<double2*>(p)[k] = V;
+    }
+    // one vector <-> its lower amplitude and, in fp32, its upper one
+    static __device__ __forceinline__ void unpack(Vec V, cplx<R>& lo, cplx<R>& hi)
+    {
+        lo = cplx<R>(V.x, V.y);
+        if constexpr (F32) hi = cplx<R>(V.z, V.w);
+    }
+    static __device__ __forceinline__ Vec pack(cplx<R> lo, cplx<R> hi)
+    {
+        if constexpr (F32) return make_float4(lo.re, lo.im, hi.re, hi.im);
+        else return make_double2(lo.re, lo.im);
+    }
+
+    // the a lanes alone (MODE -1)
+    template <bool NT = false> __device__ __forceinline__ void load(const cplx<R>* p, cplx<R> (&a)[L]) const
+    {
+        static_assert(MODE != 2, "in MODE 2 the vector's upper half is b");
+        unpack(ldv<NT>(p, ia), a[0], a[L - 1]);
+    }
+    template <bool NT = false> __device__ __forceinline__ void store(cplx<R>* p, const cplx<R> (&a)[L]) const
+    {
+        stv<NT>(p, ia, pack(a[0], a[L - 1]));
+    }
+
+    template <bool NT = false>
+    __device__ __forceinline__ void load(const cplx<R>* p, cplx<R> (&a)[L], cplx<R> (&b)[L]) const
+    {
+        if constexpr (MODE == 2) {
+            unpack(ldv<NT>(p, ia), a[0], b[0]);
+        } else {
+            load<NT>(p, a);
+            Vec B = ldv<NT>(p, ib);
+            if constexpr (TWO) B = swapped ? make_float4(B.z, B.w, B.x, B.y) : B;
+            unpack(B, b[0], b[L - 1]);
+        }
+    }
+    template <bool NT = false>
+    __device__ __forceinline__ void store(cplx<R>* p, const cplx<R> (&a)[L], const cplx<R> (&b)[L]) const
+    {
+        if constexpr (MODE == 2) {
+            stv<NT>(p, ia, pack(a[0], b[0]));
+        } else {
+            Vec B = pack(b[0], b[L - 1]);
+            if constexpr (TWO) B = swapped ? make_float4(B.z, B.w, B.x, B.y) : B;
+            store<NT>(p, a);
+            stv<NT>(p, ib, B);
+        }
+    }
+};
+
+// f(l) for every lane l < L, l a compile-time constant. A `#pragma unroll`
+// loop over the lanes computes the same, but the lane arrays then reach
+// registers only after the unroller has run, and the fp32 kernels come out
+// with up to ten more VGPRs (profiles/PROF_PAIR_WALK.md).
+template <int L, typename F> __device__ __forceinline__ void forLanes(F&& f)
+{
+    f(std::integral_constant<int, 0>{});
+    if constexpr (L == 2) f(std::integral_constant<int, 1>{});
+}
+
+template <int MODE> using PairMode = std::integral_constant<int, MODE>;
+
+// The mode of (x, nAmps) as a compile-time constant:
+// f(PairMode<MODE>{}, nItems, topPow), topPow the top bit of x.
+template <typename R, typename F> static void pauliPairDispatch(bitCapInt x, bitCapInt nAmps, F&& f)
+{
+    constexpr bool F32 = sizeof(R) == 4;
+    if (!x) {
+        f(PairMode<-1>{}, F32 ? (nAmps >> 1u) : nAmps, (bitCapInt)0);
+        return;
+    }
+    const bitCapInt topPow = ONE_BCI << (63 - __builtin_clzll(x));
+    if constexpr (!F32) {
+        f(PairMode<0>{}, nAmps >> 1u, topPow);
+    } else if (x == 1u) {
+        f(PairMode<2>{}, nAmps >> 1u, topPow);
+    } else {
+        f(PairMode<1>{}, nAmps >> 2u, topPow);
+    }
+}
+
+// a runtime flag as a template argument: f(std::true_type{}) or
+// f(std::false_type{}); with CAN false the true form is never instantiated
+template <bool CAN = true, typename F> static void liftBool(bool flag, F&& f)
+{
+    if constexpr (CAN) {
+        if (flag) {
+            f(std::true_type{});
+            return;
+        }
+    }
+    f(std::false_type{});
+}
+
+// grid of the pair kernels: one partial per block, and the QRACK_GPU_BLOCKS
+// cap so that a small state can drive the stride loop
+static inline int gridForPairs(bitCapInt nItems)
+{
+    int grid = gridForReduce(nItems);
+    const int cap = maxBlocks();
+    if (cap > 0 && grid > cap) grid = cap;
+    return grid;
+}
 
 // block sum in a fixed order: wave shuffle -> LDS -> one double
 __device__ __forceinline__ void blockSumStore(double s, double* dst)
@@ -4123,385 +4274,6 @@ __device__ __forceinline__ void blockSumStore(double s, double* dst)
         t = waveReduceSum(t);
         if (lane == 0) *dst = t;
     }
-}
-
-// weights of index i (even when TWO) and, when TWO, of i + 1
-template <bool TWO, typename ARGS>
-__device__ __forceinline__ void pauliWeights(const ARGS& a, int first, int last, bitCapInt i,
-    double& w0, double& w1)
-{
-    w0 = 0;
-    w1 = 0;
-    for (int t = first; t < last; ++t) {
-        const bitCapInt z = a.z[t];
-        const double c = a.w[t];
-        const unsigned p0 = __popcll(i & z) & 1u;
-        w0 += p0 ? -c : c;
-        if (TWO) {
-            const unsigned p1 = p0 ^ (unsigned)(z & 1u);
-            w1 += p1 ? -c : c;
-        }
-    }
-}
-
-// 2 Re((wr + i wi) conj(b) a)
-template <typename R>
-__device__ __forceinline__ double pauliPair(R are, R aim, R bre, R bim, double wr, double wi)
-{
-    const R pr = bre * are + bim * aim;
-    const R pi = bre * aim - bim * are;
-    return 2.0 * (wr * (double)pr - wi * (double)pi);
-}
-
-// MODE 0: one pair per item (fp64); 1: two pairs per item (fp32, x != 1);
-// 2: fp32, x == 1
-template <typename R, int MODE>
-__global__ void k_pauli_group(const cplx<R>* sv, PauliArgs a, bitCapInt nItems, bitCapInt topPow,
-    double* partials)
-{
-    double s = 0;
-    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
-    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        double wr0, wr1, wi0, wi1;
-        if constexpr (MODE == 0) {
-            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
-            const double2 A = reinterpret_cast<const double2*>(sv)[i];
-            const double2 B = reinterpret_cast<const double2*>(sv)[i ^ a.x];
-            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            s += pauliPair<double>(A.x, A.y, B.x, B.y, wr0, wi0);
-        } else if constexpr (MODE == 1) {
-            const bitCapInt j = v << 1u;
-            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
-            const float4 A = reinterpret_cast<const float4*>(sv)[i >> 1u];
-            float4 B = reinterpret_cast<const float4*>(sv)[(i ^ a.x) >> 1u];
-            if (a.x & 1u) B = make_float4(B.z, B.w, B.x, B.y);
-            pauliWeights<true>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<true>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            s += pauliPair<float>(A.x, A.y, B.x, B.y, wr0, wi0);
-            s += pauliPair<float>(A.z, A.w, B.z, B.w, wr1, wi1);
-        } else {
-            const bitCapInt i = v << 1u;
-            const float4 A = reinterpret_cast<const float4*>(sv)[v];
-            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            s += pauliPair<float>(A.x, A.y, A.z, A.w, wr0, wi0);
-        }
-    }
-    blockSumStore(s, partials + blockIdx.x);
-}
-
-// x == 0: sum_i |psi[i]|^2 sum_t c_t (-1)^popcount(i&z_t)
-template <typename R> __global__ void k_pauli_diag(const cplx<R>* sv, PauliArgs a, bitCapInt nItems, double* partials)
-{
-    double s = 0;
-    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
-    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        double w0, w1;
-        if constexpr (sizeof(R) == 4) {
-            const float4 A = reinterpret_cast<const float4*>(sv)[v];
-            pauliWeights<true>(a, 0, a.nTerms, v << 1u, w0, w1);
-            s += w0 * (double)(A.x * A.x + A.y * A.y) + w1 * (double)(A.z * A.z + A.w * A.w);
-        } else {
-            const double2 A = reinterpret_cast<const double2*>(sv)[v];
-            pauliWeights<false>(a, 0, a.nTerms, v, w0, w1);
-            s += w0 * (A.x * A.x + A.y * A.y);
-        }
-    }
-    blockSumStore(s, partials + blockIdx.x);
-}
-
-// stage 2: fold one launch's block partials, in a fixed order, into one double
-__global__ void k_pauli_finish(const double* partials, int n, double* result)
-{
-    double s = 0;
-    for (int k = threadIdx.x; k < n; k += QA_BLOCK) s += partials[k];
-    blockSumStore(s, result);
-}
-
-template <typename R>
-void launchPauliGroup(const cplx<R>* sv, const PauliArgs& a, double* partialsDev,
-    double* resultDev, hipStream_t stream)
-{
-    // an item is one 16-byte load per stream: two amplitudes in fp32, one in fp64
-    bitCapInt nItems;
-    int grid;
-    if (!a.x) {
-        nItems = (sizeof(R) == 4) ? (a.nAmps >> 1u) : a.nAmps;
-        grid = gridForReduce(nItems);
-        hipLaunchKernelGGL((k_pauli_diag<R>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv, a, nItems,
-            partialsDev);
-    } else {
-        const bitCapInt topPow = ONE_BCI << (63 - __builtin_clzll(a.x));
-        if constexpr (sizeof(R) == 4) {
-            if (a.x == 1u) {
-                nItems = a.nAmps >> 1u;
-                grid = gridForReduce(nItems);
-                hipLaunchKernelGGL((k_pauli_group<R, 2>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv,
-                    a, nItems, topPow, partialsDev);
-            } else {
-                nItems = a.nAmps >> 2u;
-                grid = gridForReduce(nItems);
-                hipLaunchKernelGGL((k_pauli_group<R, 1>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv,
-                    a, nItems, topPow, partialsDev);
-            }
-        } else {
-            nItems = a.nAmps >> 1u;
-            grid = gridForReduce(nItems);
-            hipLaunchKernelGGL((k_pauli_group<R, 0>), dim3(grid), dim3(QA_BLOCK), 0, stream, sv, a,
-                nItems, topPow, partialsDev);
-        }
-    }
-    hipLaunchKernelGGL(
-        k_pauli_finish, dim3(1), dim3(QA_BLOCK), 0, stream, partialsDev, grid, resultDev);
-}
-
-// ---- Pauli-sum evolution ---------------------------------------------------------
-//
-// exp(-i tau sum_t w_t P_t) for terms that share x, applied in place: the
-// per-pair algebra is in qengine.hpp (pauliEvolvePlan). Addressing is that of
-// k_pauli_group, so every amplitude is loaded once and stored once by exactly
-// one thread; where the partner vector's halves were swapped on load (fp32,
-// bit 0 of x set) they are swapped back before the store.
-
-// c + i s = e^{i angle} for segment k (its terms start at `first`) at index i,
-// and at i + 1 when TWO. SINGLE: the segment is one term, |angle| is constant
-// and the host's cos / sin are used, so only sin's sign depends on i. Otherwise
-// the angle is summed in double and sincos is the accurate double one: the
-// native fast sincos is off by ~10 eps (ARCHITECTURE.md, cphase_pairs).
-template <bool SINGLE, bool TWO, typename R>
-__device__ __forceinline__ void pauliEvolveCS(const PauliEvolveArgs& a, int k, int first, bitCapInt i,
-    R& c0, R& s0, R& c1, R& s1)
-{
-    if constexpr (SINGLE) {
-        const bitCapInt z = a.z[first];
-        const unsigned p0 = __popcll(i & z) & 1u;
-        const R c = (R)a.segCos[k];
-        const R s = (R)a.segSin[k];
-        c0 = c;
-        s0 = p0 ? -s : s;
-        if (TWO) {
-            c1 = c;
-            s1 = (p0 ^ (unsigned)(z & 1u)) ? -s : s;
-        }
-    } else {
-        double w0, w1, sd, cd;
-        pauliWeights<TWO>(a, first, a.segEnd[k], i, w0, w1);
-        sincos(w0, &sd, &cd);
-        c0 = (R)cd;
-        s0 = (R)sd;
-        if (TWO) {
-            sincos(w1, &sd, &cd);
-            c1 = (R)cd;
-            s1 = (R)sd;
-        }
-    }
-}
-
-// re set: (a, b) <- (c a - i s b, c b - i s a); im set: (a, b) <- (c a - s b, c b + s a)
-template <typename R>
-__device__ __forceinline__ void pauliEvolveRot(bool im, R c, R s, R& ar, R& ai, R& br, R& bi)
-{
-    const R par = ar, pai = ai, pbr = br, pbi = bi;
-    if (im) {
-        ar = c * par - s * pbr;
-        ai = c * pai - s * pbi;
-        br = c * pbr + s * par;
-        bi = c * pbi + s * pai;
-    } else {
-        ar = c * par + s * pbi;
-        ai = c * pai - s * pbr;
-        br = c * pbr + s * pai;
-        bi = c * pbi - s * par;
-    }
-}
-
-template <typename R> __device__ __forceinline__ void pauliEvolveScale(R pr, R pi, R& re, R& im)
-{
-    const R t = pr * re - pi * im;
-    im = pr * im + pi * re;
-    re = t;
-}
-
-// MODE as in k_pauli_group: 0 = one pair per item (fp64); 1 = two pairs per
-// item (fp32, x != 1); 2 = fp32, x == 1 (the pair is one vector)
-template <typename R, int MODE, bool SINGLE, bool NT>
-__global__ void k_pauli_evolve(cplx<R>* sv, PauliEvolveArgs a, bitCapInt nItems, bitCapInt topPow)
-{
-    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
-    const R pr = (R)a.phaseRe, pi = (R)a.phaseIm;
-    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        R c0, s0, c1, s1;
-        if constexpr (MODE == 0) {
-            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
-            double2* p = reinterpret_cast<double2*>(sv);
-            double2 A = p[i];
-            double2 B = p[i ^ a.x];
-            int first = 0;
-            for (int k = 0; k < a.nSeg; ++k) {
-                pauliEvolveCS<SINGLE, false, double>(a, k, first, i, c0, s0, c1, s1);
-                pauliEvolveRot<double>(a.segIm[k] != 0, c0, s0, A.x, A.y, B.x, B.y);
-                first = a.segEnd[k];
-            }
-            if (a.hasPhase) {
-                pauliEvolveScale<double>(pr, pi, A.x, A.y);
-                pauliEvolveScale<double>(pr, pi, B.x, B.y);
-            }
-            p[i] = A;
-            p[i ^ a.x] = B;
-        } else if constexpr (MODE == 1) {
-            const bitCapInt j = v << 1u;
-            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
-            float4* p = reinterpret_cast<float4*>(sv);
-            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
-            float4 A = ld4<NT>(p + ia);
-            float4 B = ld4<NT>(p + ib);
-            const bool swapped = (a.x & 1u) != 0;
-            if (swapped) B = make_float4(B.z, B.w, B.x, B.y);
-            int first = 0;
-            for (int k = 0; k < a.nSeg; ++k) {
-                pauliEvolveCS<SINGLE, true, float>(a, k, first, i, c0, s0, c1, s1);
-                const bool im = a.segIm[k] != 0;
-                pauliEvolveRot<float>(im, c0, s0, A.x, A.y, B.x, B.y);
-                pauliEvolveRot<float>(im, c1, s1, A.z, A.w, B.z, B.w);
-                first = a.segEnd[k];
-            }
-            if (a.hasPhase) {
-                pauliEvolveScale<float>(pr, pi, A.x, A.y);
-                pauliEvolveScale<float>(pr, pi, A.z, A.w);
-                pauliEvolveScale<float>(pr, pi, B.x, B.y);
-                pauliEvolveScale<float>(pr, pi, B.z, B.w);
-            }
-            if (swapped) B = make_float4(B.z, B.w, B.x, B.y);
-            st4<NT>(p + ia, A);
-            st4<NT>(p + ib, B);
-        } else {
-            float4* p = reinterpret_cast<float4*>(sv);
-            const bitCapInt i = v << 1u;
-            float4 A = ld4<NT>(p + v);
-            int first = 0;
-            for (int k = 0; k < a.nSeg; ++k) {
-                pauliEvolveCS<SINGLE, false, float>(a, k, first, i, c0, s0, c1, s1);
-                pauliEvolveRot<float>(a.segIm[k] != 0, c0, s0, A.x, A.y, A.z, A.w);
-                first = a.segEnd[k];
-            }
-            if (a.hasPhase) {
-                pauliEvolveScale<float>(pr, pi, A.x, A.y);
-                pauliEvolveScale<float>(pr, pi, A.z, A.w);
-            }
-            st4<NT>(p + v, A);
-        }
-    }
-}
-
-// x == 0: psi[i] *= e^{-i angle(i)}, angle(i) the signed sum of the one segment
-template <typename R, bool SINGLE, bool NT>
-__global__ void k_pauli_evolve_diag(cplx<R>* sv, PauliEvolveArgs a, bitCapInt nItems)
-{
-    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
-    const R pr = (R)a.phaseRe, pi = (R)a.phaseIm;
-    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        R c0, s0, c1, s1;
-        if constexpr (sizeof(R) == 4) {
-            float4* p = reinterpret_cast<float4*>(sv);
-            float4 A = ld4<NT>(p + v);
-            pauliEvolveCS<SINGLE, true, float>(a, 0, 0, v << 1u, c0, s0, c1, s1);
-            pauliEvolveScale<float>(c0, -s0, A.x, A.y);
-            pauliEvolveScale<float>(c1, -s1, A.z, A.w);
-            if (a.hasPhase) {
-                pauliEvolveScale<float>(pr, pi, A.x, A.y);
-                pauliEvolveScale<float>(pr, pi, A.z, A.w);
-            }
-            st4<NT>(p + v, A);
-        } else {
-            double2* p = reinterpret_cast<double2*>(sv);
-            double2 A = p[v];
-            pauliEvolveCS<SINGLE, false, double>(a, 0, 0, v, c0, s0, c1, s1);
-            pauliEvolveScale<double>(c0, -s0, A.x, A.y);
-            if (a.hasPhase) pauliEvolveScale<double>(pr, pi, A.x, A.y);
-            p[v] = A;
-        }
-    }
-}
-
-// pick the SINGLE / NT instantiation of one addressing mode; MODE < 0 is the
-// diagonal kernel
-template <typename R, int MODE>
-static void launchPauliEvolveMode(cplx<R>* sv, const PauliEvolveArgs& a, bitCapInt nItems,
-    bitCapInt topPow, bool single, hipStream_t stream)
-{
-    const dim3 g(gridFor(nItems)), b(QA_BLOCK);
-    // nontemporal access exists for the float4 streams only
-    const bool nt = (sizeof(R) == 4) && useNontemporal();
-#define QA_PE_LAUNCH(SINGLE, NT)                                                                    \
-    do {                                                                                            \
-        if constexpr (MODE < 0) {                                                                   \
-            hipLaunchKernelGGL((k_pauli_evolve_diag<R, SINGLE, NT>), g, b, 0, stream, sv, a, nItems); \
-        } else {                                                                                    \
-            hipLaunchKernelGGL(                                                                     \
-                (k_pauli_evolve<R, MODE, SINGLE, NT>), g, b, 0, stream, sv, a, nItems, topPow);     \
-        }                                                                                           \
-    } while (0)
-    if constexpr (sizeof(R) == 4) {
-        if (single) {
-            if (nt) QA_PE_LAUNCH(true, true);
-            else QA_PE_LAUNCH(true, false);
-        } else {
-            if (nt) QA_PE_LAUNCH(false, true);
-            else QA_PE_LAUNCH(false, false);
-        }
-    } else {
-        if (single) QA_PE_LAUNCH(true, false);
-        else QA_PE_LAUNCH(false, false);
-    }
-#undef QA_PE_LAUNCH
-}
-
-template <typename R>
-void launchPauliEvolve(cplx<R>* sv, const PauliEvolveArgs& a, hipStream_t stream)
-{
-    // the transcendental-free kernel needs every segment to hold one term
-    bool single = a.nSeg > 0;
-    for (int k = 0, first = 0; k < a.nSeg; first = a.segEnd[k++]) {
-        if (a.segEnd[k] - first != 1) single = false;
-    }
-    // an item is one 16-byte access per stream: two amplitudes in fp32, one in fp64
-    if (!a.x) {
-        launchPauliEvolveMode<R, -1>(
-            sv, a, (sizeof(R) == 4) ? (a.nAmps >> 1u) : a.nAmps, 0u, single, stream);
-        return;
-    }
-    const bitCapInt topPow = ONE_BCI << (63 - __builtin_clzll(a.x));
-    if constexpr (sizeof(R) == 4) {
-        if (a.x == 1u) {
-            launchPauliEvolveMode<R, 2>(sv, a, a.nAmps >> 1u, topPow, single, stream);
-        } else {
-            launchPauliEvolveMode<R, 1>(sv, a, a.nAmps >> 2u, topPow, single, stream);
-        }
-    } else {
-        launchPauliEvolveMode<R, 0>(sv, a, a.nAmps >> 1u, topPow, single, stream);
-    }
-}
-
-// ---- Pauli brakets, H|psi>, fused adjoint step ------------------------------------
-//
-// All three walk the pairs (i, j = i^x) of k_pauli_group / k_pauli_evolve, in
-// the same three addressing modes, so every amplitude of every vector involved
-// is loaded once (and, where written, stored once by exactly one thread).
-// With W(i) = wr(i) + i wi(i) the summed weight of a group at index i, the
-// partner's weight is conj(W(i)): a term of the re set has an even number of
-// Y factors, popcount(x & z) is even and its sign is the same at i and i^x;
-// a term of the im set has an odd number and its sign flips. No second
-// popcount over the index is needed.
-
-// reduction grid of the pair kernels: one partial per block, and the
-// QRACK_GPU_BLOCKS cap so that a small state can drive the stride loop
-static inline int gridForPairs(bitCapInt nItems)
-{
-    int grid = gridForReduce(nItems);
-    const int cap = maxBlocks();
-    if (cap > 0 && grid > cap) grid = cap;
-    return grid;
 }
 
 // block sums of a complex value in a fixed order; the two parts have an LDS
@@ -4531,112 +4303,15 @@ __device__ __forceinline__ void blockSumStore2(double re, double im, double* dst
     }
 }
 
-// pair (i, j): W conj(q) a + conj(W) conj(p) b, with a = psi[i], b = psi[j],
-// p = bra[i], q = bra[j] and W = wr + i wi; products in R, sums in double
-template <typename R>
-__device__ __forceinline__ void pauliBraketPair(R ar, R ai, R br, R bi, R pr, R pi, R qr, R qi,
-    double wr, double wi, double& re, double& im)
+// stage 2: fold one launch's block partials, in a fixed order, into one double
+__global__ void k_pauli_finish(const double* partials, int n, double* result)
 {
-    const R t1r = qr * ar + qi * ai, t1i = qr * ai - qi * ar;
-    const R t2r = pr * br + pi * bi, t2i = pr * bi - pi * br;
-    re += wr * ((double)t1r + (double)t2r) - wi * ((double)t1i - (double)t2i);
-    im += wr * ((double)t1i + (double)t2i) + wi * ((double)t1r - (double)t2r);
+    double s = 0;
+    for (int k = threadIdx.x; k < n; k += QA_BLOCK) s += partials[k];
+    blockSumStore(s, result);
 }
 
-// w conj(p) a: a diagonal term, and the identity's share of any pair
-template <typename R>
-__device__ __forceinline__ void pauliBraketDiag(R ar, R ai, R pr, R pi, double w, double& re, double& im)
-{
-    re += w * (double)(pr * ar + pi * ai);
-    im += w * (double)(pr * ai - pi * ar);
-}
-
-// <bra| sum_t c_t P_t |psi> for one group with x != 0, plus ident <bra|psi>
-template <typename R, int MODE>
-__global__ void k_pauli_braket(const cplx<R>* psi, const cplx<R>* bra, PauliArgs a, double ident,
-    bitCapInt nItems, bitCapInt topPow, double* partialsRe, double* partialsIm)
-{
-    double re = 0, im = 0;
-    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
-    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        double wr0, wr1, wi0, wi1;
-        if constexpr (MODE == 0) {
-            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
-            const double2 A = reinterpret_cast<const double2*>(psi)[i];
-            const double2 B = reinterpret_cast<const double2*>(psi)[i ^ a.x];
-            const double2 P = reinterpret_cast<const double2*>(bra)[i];
-            const double2 Q = reinterpret_cast<const double2*>(bra)[i ^ a.x];
-            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            pauliBraketPair<double>(A.x, A.y, B.x, B.y, P.x, P.y, Q.x, Q.y, wr0, wi0, re, im);
-            if (ident != 0) {
-                pauliBraketDiag<double>(A.x, A.y, P.x, P.y, ident, re, im);
-                pauliBraketDiag<double>(B.x, B.y, Q.x, Q.y, ident, re, im);
-            }
-        } else if constexpr (MODE == 1) {
-            const bitCapInt j = v << 1u;
-            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
-            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
-            const float4 A = reinterpret_cast<const float4*>(psi)[ia];
-            float4 B = reinterpret_cast<const float4*>(psi)[ib];
-            const float4 P = reinterpret_cast<const float4*>(bra)[ia];
-            float4 Q = reinterpret_cast<const float4*>(bra)[ib];
-            if (a.x & 1u) {
-                B = make_float4(B.z, B.w, B.x, B.y);
-                Q = make_float4(Q.z, Q.w, Q.x, Q.y);
-            }
-            pauliWeights<true>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<true>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            pauliBraketPair<float>(A.x, A.y, B.x, B.y, P.x, P.y, Q.x, Q.y, wr0, wi0, re, im);
-            pauliBraketPair<float>(A.z, A.w, B.z, B.w, P.z, P.w, Q.z, Q.w, wr1, wi1, re, im);
-            if (ident != 0) {
-                pauliBraketDiag<float>(A.x, A.y, P.x, P.y, ident, re, im);
-                pauliBraketDiag<float>(A.z, A.w, P.z, P.w, ident, re, im);
-                pauliBraketDiag<float>(B.x, B.y, Q.x, Q.y, ident, re, im);
-                pauliBraketDiag<float>(B.z, B.w, Q.z, Q.w, ident, re, im);
-            }
-        } else {
-            const bitCapInt i = v << 1u;
-            const float4 A = reinterpret_cast<const float4*>(psi)[v];
-            const float4 P = reinterpret_cast<const float4*>(bra)[v];
-            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            pauliBraketPair<float>(A.x, A.y, A.z, A.w, P.x, P.y, P.z, P.w, wr0, wi0, re, im);
-            if (ident != 0) {
-                pauliBraketDiag<float>(A.x, A.y, P.x, P.y, ident, re, im);
-                pauliBraketDiag<float>(A.z, A.w, P.z, P.w, ident, re, im);
-            }
-        }
-    }
-    blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
-}
-
-// x == 0: sum_i (ident + sum_t c_t (-1)^popcount(i&z_t)) conj(bra[i]) psi[i]
-template <typename R>
-__global__ void k_pauli_braket_diag(const cplx<R>* psi, const cplx<R>* bra, PauliArgs a, double ident,
-    bitCapInt nItems, double* partialsRe, double* partialsIm)
-{
-    double re = 0, im = 0;
-    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
-    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        double w0, w1;
-        if constexpr (sizeof(R) == 4) {
-            const float4 A = reinterpret_cast<const float4*>(psi)[v];
-            const float4 P = reinterpret_cast<const float4*>(bra)[v];
-            pauliWeights<true>(a, 0, a.nTerms, v << 1u, w0, w1);
-            pauliBraketDiag<float>(A.x, A.y, P.x, P.y, w0 + ident, re, im);
-            pauliBraketDiag<float>(A.z, A.w, P.z, P.w, w1 + ident, re, im);
-        } else {
-            const double2 A = reinterpret_cast<const double2*>(psi)[v];
-            const double2 P = reinterpret_cast<const double2*>(bra)[v];
-            pauliWeights<false>(a, 0, a.nTerms, v, w0, w1);
-            pauliBraketDiag<double>(A.x, A.y, P.x, P.y, w0 + ident, re, im);
-        }
-    }
-    blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
-}
-
-// stage 2: fold one launch's block partials, in a fixed order, into (re, im)
+// ... of a complex value, into (re, im)
 __global__ void k_pauli_finish2(const double* partialsRe, const double* partialsIm, int n, double* result)
 {
     double re = 0, im = 0;
@@ -4647,197 +4322,465 @@ __global__ void k_pauli_finish2(const double* partialsRe, const double* partials
     blockSumStore2(re, im, result, result + 1);
 }
 
-// items and top power of the pair walk: an item is one 16-byte access per
-// stream. mode -1 is the diagonal kernel.
-template <typename R> static int pauliPairMode(bitCapInt x, bitCapInt nAmps, bitCapInt& nItems, bitCapInt& topPow)
+// w[l] = sum_t c_t (-1)^popcount((i + l) & z_t) over terms first .. last - 1;
+// i is even when L == 2
+template <int L, typename ARGS>
+__device__ __forceinline__ void pauliWeights(const ARGS& a, int first, int last, bitCapInt i, double (&w)[L])
 {
-    if (!x) {
-        nItems = (sizeof(R) == 4) ? (nAmps >> 1u) : nAmps;
-        topPow = 0;
-        return -1;
+    w[0] = 0;
+    w[L - 1] = 0;
+    for (int t = first; t < last; ++t) {
+        const bitCapInt z = a.z[t];
+        const double c = a.w[t];
+        const unsigned p0 = __popcll(i & z) & 1u;
+        w[0] += p0 ? -c : c;
+        if constexpr (L == 2) {
+            const unsigned p1 = p0 ^ (unsigned)(z & 1u);
+            w[1] += p1 ? -c : c;
+        }
     }
-    topPow = ONE_BCI << (63 - __builtin_clzll(x));
-    if (sizeof(R) == 8) {
-        nItems = nAmps >> 1u;
-        return 0;
+}
+
+// sum of |a[l]|^2 over the lanes, and of w[l] |a[l]|^2: squares in R, the rest
+// in double
+template <typename R, int L> __device__ __forceinline__ double pauliLaneNorm(const cplx<R> (&a)[L])
+{
+    if constexpr (L == 2) return (double)norm(a[0]) + (double)norm(a[1]);
+    else return (double)norm(a[0]);
+}
+template <typename R, int L>
+__device__ __forceinline__ double pauliLaneWeightedNorm(const double (&w)[L], const cplx<R> (&a)[L])
+{
+    if constexpr (L == 2) return w[0] * (double)norm(a[0]) + w[1] * (double)norm(a[1]);
+    else return w[0] * (double)norm(a[0]);
+}
+
+// ---- Pauli-sum expectation -------------------------------------------------------
+//
+// <psi|P|psi>: for x != 0 the pair (i, i^x) contributes
+// 2 Re(w(i) conj(psi[i^x]) psi[i]) with w(i) = sum_t c_t i^ny_t (-1)^popcount(i&z_t).
+// Nothing is stored.
+
+// 2 Re((wr + i wi) conj(b) a)
+template <typename R> __device__ __forceinline__ double pauliPair(cplx<R> a, cplx<R> b, double wr, double wi)
+{
+    const R pr = b.re * a.re + b.im * a.im;
+    const R pi = b.re * a.im - b.im * a.re;
+    return 2.0 * (wr * (double)pr - wi * (double)pi);
+}
+
+template <typename R, int MODE>
+__global__ void k_pauli_group(const cplx<R>* sv, PauliArgs a, bitCapInt nItems, bitCapInt topPow,
+    double* partials)
+{
+    using Item = PairItem<R, MODE>;
+    constexpr int L = Item::L;
+    double s = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        const Item it(v, topPow, a.x);
+        cplx<R> A[L], B[L];
+        double wr[L], wi[L];
+        it.load(sv, A, B);
+        pauliWeights(a, 0, a.nRe, it.i, wr);
+        pauliWeights(a, a.nRe, a.nTerms, it.i, wi);
+        forLanes<L>([&](auto l) { s += pauliPair(A[l], B[l], wr[l], wi[l]); });
     }
-    if (x == 1u) {
-        nItems = nAmps >> 1u;
-        return 2;
+    blockSumStore(s, partials + blockIdx.x);
+}
+
+// x == 0: sum_i |psi[i]|^2 sum_t c_t (-1)^popcount(i&z_t)
+template <typename R> __global__ void k_pauli_diag(const cplx<R>* sv, PauliArgs a, bitCapInt nItems, double* partials)
+{
+    using Item = PairItem<R, -1>;
+    constexpr int L = Item::L;
+    double s = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        const Item it(v, 0u, 0u);
+        cplx<R> A[L];
+        double w[L];
+        it.load(sv, A);
+        pauliWeights(a, 0, a.nTerms, it.i, w);
+        s += pauliLaneWeightedNorm(w, A);
     }
-    nItems = nAmps >> 2u;
-    return 1;
+    blockSumStore(s, partials + blockIdx.x);
+}
+
+template <typename R>
+void launchPauliGroup(const cplx<R>* sv, const PauliArgs& a, double* partialsDev,
+    double* resultDev, hipStream_t stream)
+{
+    pauliPairDispatch<R>(a.x, a.nAmps, [&](auto mode, bitCapInt nItems, bitCapInt topPow) {
+        constexpr int MODE = decltype(mode)::value;
+        const int grid = gridForPairs(nItems);
+        const dim3 g(grid), b(QA_BLOCK);
+        if constexpr (MODE < 0) {
+            hipLaunchKernelGGL((k_pauli_diag<R>), g, b, 0, stream, sv, a, nItems, partialsDev);
+        } else {
+            hipLaunchKernelGGL((k_pauli_group<R, MODE>), g, b, 0, stream, sv, a, nItems, topPow, partialsDev);
+        }
+        hipLaunchKernelGGL(k_pauli_finish, dim3(1), b, 0, stream, partialsDev, grid, resultDev);
+    });
+}
+
+// ---- Pauli-sum evolution ---------------------------------------------------------
+//
+// exp(-i tau sum_t w_t P_t) for terms that share x, applied in place: the
+// per-pair algebra is in qengine.hpp (pauliEvolvePlan).
+
+// c[l] + i s[l] = e^{i angle} for segment k (its terms start at `first`) at
+// index i + l. SINGLE: the segment is one term, |angle| is constant and the
+// host's cos / sin are used, so only sin's sign depends on the index. Otherwise
+// the angle is summed in double and sincos is the accurate double one: the
+// native fast sincos is off by ~10 eps (ARCHITECTURE.md, cphase_pairs).
+template <bool SINGLE, int L, typename R>
+__device__ __forceinline__ void pauliEvolveCS(const PauliEvolveArgs& a, int k, int first, bitCapInt i,
+    R (&c)[L], R (&s)[L])
+{
+    if constexpr (SINGLE) {
+        const bitCapInt z = a.z[first];
+        const unsigned p0 = __popcll(i & z) & 1u;
+        const R cs = (R)a.segCos[k];
+        const R sn = (R)a.segSin[k];
+        c[0] = cs;
+        s[0] = p0 ? -sn : sn;
+        if constexpr (L == 2) {
+            c[1] = cs;
+            s[1] = (p0 ^ (unsigned)(z & 1u)) ? -sn : sn;
+        }
+    } else {
+        double w[L], sd, cd;
+        pauliWeights(a, first, a.segEnd[k], i, w);
+        forLanes<L>([&](auto l) {
+            sincos(w[l], &sd, &cd);
+            c[l] = (R)cd;
+            s[l] = (R)sd;
+        });
+    }
+}
+
+// re set: (a, b) <- (c a - i s b, c b - i s a); im set: (a, b) <- (c a - s b, c b + s a)
+template <typename R> __device__ __forceinline__ void pauliEvolveRot(bool im, R c, R s, cplx<R>& a, cplx<R>& b)
+{
+    const R par = a.re, pai = a.im, pbr = b.re, pbi = b.im;
+    if (im) {
+        a.re = c * par - s * pbr;
+        a.im = c * pai - s * pbi;
+        b.re = c * pbr + s * par;
+        b.im = c * pbi + s * pai;
+    } else {
+        a.re = c * par + s * pbi;
+        a.im = c * pai - s * pbr;
+        b.re = c * pbr + s * pai;
+        b.im = c * pbi - s * par;
+    }
+}
+
+// a <- (pr + i pi) a
+template <typename R> __device__ __forceinline__ void pauliEvolveScale(R pr, R pi, cplx<R>& a)
+{
+    const R t = pr * a.re - pi * a.im;
+    a.im = pr * a.im + pi * a.re;
+    a.re = t;
+}
+
+template <typename R, int MODE, bool SINGLE, bool NT>
+__global__ void k_pauli_evolve(cplx<R>* sv, PauliEvolveArgs a, bitCapInt nItems, bitCapInt topPow)
+{
+    using Item = PairItem<R, MODE>;
+    constexpr int L = Item::L;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    const R pr = (R)a.phaseRe, pi = (R)a.phaseIm;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        const Item it(v, topPow, a.x);
+        cplx<R> A[L], B[L];
+        it.template load<NT>(sv, A, B);
+        // Two lanes go round the segment loop as their two float4: carried as
+        // eight scalars they cost up to ten more VGPRs and a wave of occupancy
+        // (profiles/PROF_PAIR_WALK.md).
+        [[maybe_unused]] typename Item::Vec VA, VB;
+        if constexpr (L == 2) VA = Item::pack(A[0], A[1]), VB = Item::pack(B[0], B[1]);
+        int first = 0;
+        for (int k = 0; k < a.nSeg; ++k) {
+            R c[L], s[L];
+            if constexpr (L == 2) Item::unpack(VA, A[0], A[1]), Item::unpack(VB, B[0], B[1]);
+            pauliEvolveCS<SINGLE>(a, k, first, it.i, c, s);
+            const bool im = a.segIm[k] != 0;
+            forLanes<L>([&](auto l) { pauliEvolveRot(im, c[l], s[l], A[l], B[l]); });
+            first = a.segEnd[k];
+            if constexpr (L == 2) VA = Item::pack(A[0], A[1]), VB = Item::pack(B[0], B[1]);
+        }
+        if (a.hasPhase) {
+            forLanes<L>([&](auto l) { pauliEvolveScale(pr, pi, A[l]); });
+            forLanes<L>([&](auto l) { pauliEvolveScale(pr, pi, B[l]); });
+        }
+        it.template store<NT>(sv, A, B);
+    }
+}
+
+// x == 0: psi[i] *= e^{-i angle(i)}, angle(i) the signed sum of the one segment
+template <typename R, bool SINGLE, bool NT>
+__global__ void k_pauli_evolve_diag(cplx<R>* sv, PauliEvolveArgs a, bitCapInt nItems)
+{
+    using Item = PairItem<R, -1>;
+    constexpr int L = Item::L;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    const R pr = (R)a.phaseRe, pi = (R)a.phaseIm;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        const Item it(v, 0u, 0u);
+        cplx<R> A[L];
+        R c[L], s[L];
+        it.template load<NT>(sv, A);
+        pauliEvolveCS<SINGLE>(a, 0, 0, it.i, c, s);
+        forLanes<L>([&](auto l) { s[l] = -s[l]; });
+        forLanes<L>([&](auto l) { pauliEvolveScale(c[l], s[l], A[l]); });
+        if (a.hasPhase) {
+            forLanes<L>([&](auto l) { pauliEvolveScale(pr, pi, A[l]); });
+        }
+        it.template store<NT>(sv, A);
+    }
+}
+
+template <typename R>
+void launchPauliEvolve(cplx<R>* sv, const PauliEvolveArgs& a, hipStream_t stream)
+{
+    // the transcendental-free kernel needs every segment to hold one term
+    bool single = a.nSeg > 0;
+    for (int k = 0, first = 0; k < a.nSeg; first = a.segEnd[k++]) {
+        if (a.segEnd[k] - first != 1) single = false;
+    }
+    pauliPairDispatch<R>(a.x, a.nAmps, [&](auto mode, bitCapInt nItems, bitCapInt topPow) {
+        liftBool(single, [&](auto sg) {
+            liftBool<sizeof(R) == 4>(useNontemporal(), [&](auto nt) {
+                constexpr int MODE = decltype(mode)::value;
+                constexpr bool SINGLE = decltype(sg)::value, NT = decltype(nt)::value;
+                const dim3 g(gridFor(nItems)), b(QA_BLOCK);
+                if constexpr (MODE < 0) {
+                    hipLaunchKernelGGL((k_pauli_evolve_diag<R, SINGLE, NT>), g, b, 0, stream, sv, a, nItems);
+                } else {
+                    hipLaunchKernelGGL(
+                        (k_pauli_evolve<R, MODE, SINGLE, NT>), g, b, 0, stream, sv, a, nItems, topPow);
+                }
+            });
+        });
+    });
+}
+
+// ---- Pauli brakets, H|psi>, fused adjoint step ------------------------------------
+//
+// With W(i) = wr(i) + i wi(i) the summed weight of a group at index i, the
+// partner's weight is conj(W(i)): a term of the re set has an even number of
+// Y factors, popcount(x & z) is even and its sign is the same at i and i^x;
+// a term of the im set has an odd number and its sign flips. No second
+// popcount over the index is needed.
+
+// pair (i, j): W conj(q) a + conj(W) conj(p) b, with a = psi[i], b = psi[j],
+// p = bra[i], q = bra[j] and W = wr + i wi; products in R, sums in double
+template <typename R>
+__device__ __forceinline__ void pauliBraketPair(cplx<R> a, cplx<R> b, cplx<R> p, cplx<R> q, double wr, double wi,
+    double& re, double& im)
+{
+    const R t1r = q.re * a.re + q.im * a.im, t1i = q.re * a.im - q.im * a.re;
+    const R t2r = p.re * b.re + p.im * b.im, t2i = p.re * b.im - p.im * b.re;
+    re += wr * ((double)t1r + (double)t2r) - wi * ((double)t1i - (double)t2i);
+    im += wr * ((double)t1i + (double)t2i) + wi * ((double)t1r - (double)t2r);
+}
+
+// w conj(p) a: a diagonal term, and the identity's share of any pair
+template <typename R>
+__device__ __forceinline__ void pauliBraketDiag(cplx<R> a, cplx<R> p, double w, double& re, double& im)
+{
+    re += w * (double)(p.re * a.re + p.im * a.im);
+    im += w * (double)(p.re * a.im - p.im * a.re);
+}
+
+// <bra| sum_t c_t P_t |psi> for one group with x != 0, plus ident <bra|psi>
+template <typename R, int MODE>
+__global__ void k_pauli_braket(const cplx<R>* psi, const cplx<R>* bra, PauliArgs a, double ident,
+    bitCapInt nItems, bitCapInt topPow, double* partialsRe, double* partialsIm)
+{
+    using Item = PairItem<R, MODE>;
+    constexpr int L = Item::L;
+    double re = 0, im = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        const Item it(v, topPow, a.x);
+        cplx<R> A[L], B[L], P[L], Q[L];
+        double wr[L], wi[L];
+        it.load(psi, A, B);
+        it.load(bra, P, Q);
+        pauliWeights(a, 0, a.nRe, it.i, wr);
+        pauliWeights(a, a.nRe, a.nTerms, it.i, wi);
+        forLanes<L>([&](auto l) { pauliBraketPair(A[l], B[l], P[l], Q[l], wr[l], wi[l], re, im); });
+        if (ident != 0) {
+            forLanes<L>([&](auto l) { pauliBraketDiag(A[l], P[l], ident, re, im); });
+            forLanes<L>([&](auto l) { pauliBraketDiag(B[l], Q[l], ident, re, im); });
+        }
+    }
+    blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
+}
+
+// x == 0: sum_i (ident + sum_t c_t (-1)^popcount(i&z_t)) conj(bra[i]) psi[i]
+template <typename R>
+__global__ void k_pauli_braket_diag(const cplx<R>* psi, const cplx<R>* bra, PauliArgs a, double ident,
+    bitCapInt nItems, double* partialsRe, double* partialsIm)
+{
+    using Item = PairItem<R, -1>;
+    constexpr int L = Item::L;
+    double re = 0, im = 0;
+    const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
+    for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
+        const Item it(v, 0u, 0u);
+        cplx<R> A[L], P[L];
+        double w[L];
+        it.load(psi, A);
+        it.load(bra, P);
+        pauliWeights(a, 0, a.nTerms, it.i, w);
+        forLanes<L>([&](auto l) { pauliBraketDiag(A[l], P[l], w[l] + ident, re, im); });
+    }
+    blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
 }
 
 template <typename R>
 void launchPauliBraket(const cplx<R>* psi, const cplx<R>* bra, const PauliArgs& a, double ident,
     double* partialsDev, double* resultDev, hipStream_t stream)
 {
-    bitCapInt nItems, topPow;
-    const int mode = pauliPairMode<R>(a.x, a.nAmps, nItems, topPow);
-    const int grid = gridForPairs(nItems);
     double* pRe = partialsDev;
     double* pIm = partialsDev + QA_REDUCE_MAX_BLOCKS;
-    const dim3 g(grid), b(QA_BLOCK);
-    if (mode < 0) {
-        hipLaunchKernelGGL((k_pauli_braket_diag<R>), g, b, 0, stream, psi, bra, a, ident, nItems, pRe, pIm);
-    } else if constexpr (sizeof(R) == 4) {
-        if (mode == 2) {
-            hipLaunchKernelGGL(
-                (k_pauli_braket<R, 2>), g, b, 0, stream, psi, bra, a, ident, nItems, topPow, pRe, pIm);
+    pauliPairDispatch<R>(a.x, a.nAmps, [&](auto mode, bitCapInt nItems, bitCapInt topPow) {
+        constexpr int MODE = decltype(mode)::value;
+        const int grid = gridForPairs(nItems);
+        const dim3 g(grid), b(QA_BLOCK);
+        if constexpr (MODE < 0) {
+            hipLaunchKernelGGL((k_pauli_braket_diag<R>), g, b, 0, stream, psi, bra, a, ident, nItems, pRe, pIm);
         } else {
             hipLaunchKernelGGL(
-                (k_pauli_braket<R, 1>), g, b, 0, stream, psi, bra, a, ident, nItems, topPow, pRe, pIm);
+                (k_pauli_braket<R, MODE>), g, b, 0, stream, psi, bra, a, ident, nItems, topPow, pRe, pIm);
+        }
+        hipLaunchKernelGGL(k_pauli_finish2, dim3(1), b, 0, stream, pRe, pIm, grid, resultDev);
+    });
+}
+
+// d <- d + (wr + i wi) a, everything in R
+template <typename R> __device__ __forceinline__ void pauliApplyMad(R wr, R wi, cplx<R> a, cplx<R>& d)
+{
+    d.re += wr * a.re - wi * a.im;
+    d.im += wr * a.im + wi * a.re;
+}
+
+// d <- d - c p for one amplitude a of u, and the share - c Re(conj(a) p) of A
+template <typename R>
+__device__ __forceinline__ void krylovPrev(cplx<R> a, cplx<R> p, R c, double cd, cplx<R>& d, double& s)
+{
+    d.re -= c * p.re;
+    d.im -= c * p.im;
+    s -= cd * (double)(a.re * p.re + a.im * p.im);
+}
+
+// One item of dest (+)= (sum_t c_t P_t) psi for a group with x != 0: dest[i]
+// takes W(j) psi[j] and dest[j] takes W(i) psi[i]. FIRST: dest is written
+// without being read, and ident * psi rides along (psi[i] and psi[j] are in
+// registers). KRYLOV (k_krylov_apply, below) adds to s the pair's share
+// 2 Re(W conj(psi[j]) psi[i]) + ident (|psi[i]|^2 + |psi[j]|^2) of Re <psi|dest>
+// and, when FIRST, takes - bcoef * prev from a third stream (prev == nullptr:
+// none).
+template <typename R, int MODE, bool FIRST, bool KRYLOV>
+__device__ __forceinline__ void pauliApplyItem(const cplx<R>* psi, const cplx<R>* prev, cplx<R>* dest,
+    const PauliArgs& a, double ident, double bcoef, bitCapInt v, bitCapInt topPow, double& s)
+{
+    using Item = PairItem<R, MODE>;
+    constexpr int L = Item::L;
+    const Item it(v, topPow, a.x);
+    cplx<R> A[L], B[L], DA[L], DB[L];
+    double wr[L], wi[L];
+    it.load(psi, A, B);
+    pauliWeights(a, 0, a.nRe, it.i, wr);
+    pauliWeights(a, a.nRe, a.nTerms, it.i, wi);
+    if constexpr (KRYLOV) {
+        forLanes<L>([&](auto l) { s += pauliPair(A[l], B[l], wr[l], wi[l]); });
+    }
+    if constexpr (FIRST) {
+        const R id = (R)ident;
+        forLanes<L>([&](auto l) {
+            DA[l] = cplx<R>(id * A[l].re, id * A[l].im);
+            DB[l] = cplx<R>(id * B[l].re, id * B[l].im);
+        });
+        if constexpr (KRYLOV) {
+            s += ident * (pauliLaneNorm(A) + pauliLaneNorm(B));
+            if (prev) {
+                const R bc = (R)bcoef;
+                cplx<R> P[L], Q[L];
+                it.load(prev, P, Q);
+                forLanes<L>([&](auto l) { krylovPrev(A[l], P[l], bc, bcoef, DA[l], s); });
+                forLanes<L>([&](auto l) { krylovPrev(B[l], Q[l], bc, bcoef, DB[l], s); });
+            }
         }
     } else {
-        hipLaunchKernelGGL(
-            (k_pauli_braket<R, 0>), g, b, 0, stream, psi, bra, a, ident, nItems, topPow, pRe, pIm);
+        it.load(dest, DA, DB);
     }
-    hipLaunchKernelGGL(k_pauli_finish2, dim3(1), dim3(QA_BLOCK), 0, stream, pRe, pIm, grid, resultDev);
+    forLanes<L>([&](auto l) { pauliApplyMad((R)wr[l], -(R)wi[l], B[l], DA[l]); });
+    forLanes<L>([&](auto l) { pauliApplyMad((R)wr[l], (R)wi[l], A[l], DB[l]); });
+    it.store(dest, DA, DB);
 }
 
-// (re, im) <- (re, im) + (wr + i wi) (ar + i ai), everything in R
-template <typename R>
-__device__ __forceinline__ void pauliApplyMad(R wr, R wi, R ar, R ai, R& re, R& im)
+// x == 0: dest[i] (+)= W(i) psi[i] with W(i) = sum_t c_t (-1)^popcount(i&z_t),
+// plus ident when FIRST; KRYLOV's share is W(i) |psi[i]|^2
+template <typename R, bool FIRST, bool KRYLOV>
+__device__ __forceinline__ void pauliApplyDiagItem(const cplx<R>* psi, const cplx<R>* prev, cplx<R>* dest,
+    const PauliArgs& a, double ident, double bcoef, bitCapInt v, double& s)
 {
-    re += wr * ar - wi * ai;
-    im += wr * ai + wi * ar;
+    using Item = PairItem<R, -1>;
+    constexpr int L = Item::L;
+    const Item it(v, 0u, 0u);
+    cplx<R> A[L], D[L];
+    double w[L];
+    it.load(psi, A);
+    pauliWeights(a, 0, a.nTerms, it.i, w);
+    if constexpr (FIRST) {
+        forLanes<L>([&](auto l) { w[l] += ident; });
+    }
+    if constexpr (KRYLOV) {
+        s += pauliLaneWeightedNorm(w, A);
+    }
+    if constexpr (FIRST) {
+        forLanes<L>([&](auto l) { D[l] = cplx<R>((R)w[l] * A[l].re, (R)w[l] * A[l].im); });
+        if constexpr (KRYLOV) {
+            if (prev) {
+                const R bc = (R)bcoef;
+                cplx<R> P[L];
+                it.load(prev, P);
+                forLanes<L>([&](auto l) { krylovPrev(A[l], P[l], bc, bcoef, D[l], s); });
+            }
+        }
+    } else {
+        it.load(dest, D);
+        forLanes<L>([&](auto l) {
+            D[l].re += (R)w[l] * A[l].re;
+            D[l].im += (R)w[l] * A[l].im;
+        });
+    }
+    it.store(dest, D);
 }
 
-// dest (+)= (sum_t c_t P_t) psi for one group with x != 0: dest[i] takes
-// W(j) psi[j] and dest[j] takes W(i) psi[i]. FIRST: dest is written without
-// being read, and ident * psi rides along (psi[i] and psi[j] are in registers).
 template <typename R, int MODE, bool FIRST>
 __global__ void k_pauli_apply(const cplx<R>* psi, cplx<R>* dest, PauliArgs a, double ident,
     bitCapInt nItems, bitCapInt topPow)
 {
+    double unused = 0;
     const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
-    const R id = (R)ident;
     for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        double wr0, wr1, wi0, wi1;
-        if constexpr (MODE == 0) {
-            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
-            const double2 A = reinterpret_cast<const double2*>(psi)[i];
-            const double2 B = reinterpret_cast<const double2*>(psi)[i ^ a.x];
-            double2* d = reinterpret_cast<double2*>(dest);
-            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            double2 DA, DB;
-            if constexpr (FIRST) {
-                DA = make_double2(id * A.x, id * A.y);
-                DB = make_double2(id * B.x, id * B.y);
-            } else {
-                DA = d[i];
-                DB = d[i ^ a.x];
-            }
-            pauliApplyMad<double>(wr0, -wi0, B.x, B.y, DA.x, DA.y);
-            pauliApplyMad<double>(wr0, wi0, A.x, A.y, DB.x, DB.y);
-            d[i] = DA;
-            d[i ^ a.x] = DB;
-        } else if constexpr (MODE == 1) {
-            const bitCapInt j = v << 1u;
-            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
-            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
-            const float4 A = reinterpret_cast<const float4*>(psi)[ia];
-            float4 B = reinterpret_cast<const float4*>(psi)[ib];
-            float4* d = reinterpret_cast<float4*>(dest);
-            const bool swapped = (a.x & 1u) != 0;
-            if (swapped) B = make_float4(B.z, B.w, B.x, B.y);
-            pauliWeights<true>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<true>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            float4 DA, DB;
-            if constexpr (FIRST) {
-                DA = make_float4(id * A.x, id * A.y, id * A.z, id * A.w);
-                DB = make_float4(id * B.x, id * B.y, id * B.z, id * B.w);
-            } else {
-                DA = d[ia];
-                DB = d[ib];
-                if (swapped) DB = make_float4(DB.z, DB.w, DB.x, DB.y);
-            }
-            pauliApplyMad<float>((float)wr0, -(float)wi0, B.x, B.y, DA.x, DA.y);
-            pauliApplyMad<float>((float)wr1, -(float)wi1, B.z, B.w, DA.z, DA.w);
-            pauliApplyMad<float>((float)wr0, (float)wi0, A.x, A.y, DB.x, DB.y);
-            pauliApplyMad<float>((float)wr1, (float)wi1, A.z, A.w, DB.z, DB.w);
-            if (swapped) DB = make_float4(DB.z, DB.w, DB.x, DB.y);
-            d[ia] = DA;
-            d[ib] = DB;
-        } else {
-            const bitCapInt i = v << 1u;
-            const float4 A = reinterpret_cast<const float4*>(psi)[v];
-            float4* d = reinterpret_cast<float4*>(dest);
-            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            float4 D;
-            if constexpr (FIRST) {
-                D = make_float4(id * A.x, id * A.y, id * A.z, id * A.w);
-            } else {
-                D = d[v];
-            }
-            pauliApplyMad<float>((float)wr0, -(float)wi0, A.z, A.w, D.x, D.y);
-            pauliApplyMad<float>((float)wr0, (float)wi0, A.x, A.y, D.z, D.w);
-            d[v] = D;
-        }
+        pauliApplyItem<R, MODE, FIRST, false>(psi, nullptr, dest, a, ident, 0.0, v, topPow, unused);
     }
 }
 
-// x == 0: dest[i] (+)= (sum_t c_t (-1)^popcount(i&z_t)) psi[i]; FIRST as above
 template <typename R, bool FIRST>
 __global__ void k_pauli_apply_diag(const cplx<R>* psi, cplx<R>* dest, PauliArgs a, double ident, bitCapInt nItems)
 {
+    double unused = 0;
     const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
     for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        double w0, w1;
-        if constexpr (sizeof(R) == 4) {
-            const float4 A = reinterpret_cast<const float4*>(psi)[v];
-            float4* d = reinterpret_cast<float4*>(dest);
-            pauliWeights<true>(a, 0, a.nTerms, v << 1u, w0, w1);
-            if constexpr (FIRST) {
-                const float f0 = (float)(w0 + ident), f1 = (float)(w1 + ident);
-                d[v] = make_float4(f0 * A.x, f0 * A.y, f1 * A.z, f1 * A.w);
-            } else {
-                const float f0 = (float)w0, f1 = (float)w1;
-                float4 D = d[v];
-                D.x += f0 * A.x;
-                D.y += f0 * A.y;
-                D.z += f1 * A.z;
-                D.w += f1 * A.w;
-                d[v] = D;
-            }
-        } else {
-            const double2 A = reinterpret_cast<const double2*>(psi)[v];
-            double2* d = reinterpret_cast<double2*>(dest);
-            pauliWeights<false>(a, 0, a.nTerms, v, w0, w1);
-            if constexpr (FIRST) {
-                d[v] = make_double2((w0 + ident) * A.x, (w0 + ident) * A.y);
-            } else {
-                double2 D = d[v];
-                D.x += w0 * A.x;
-                D.y += w0 * A.y;
-                d[v] = D;
-            }
-        }
-    }
-}
-
-template <typename R, bool FIRST>
-static void launchPauliApplyFirst(const cplx<R>* psi, cplx<R>* dest, const PauliArgs& a, double ident,
-    hipStream_t stream)
-{
-    bitCapInt nItems, topPow;
-    const int mode = pauliPairMode<R>(a.x, a.nAmps, nItems, topPow);
-    const dim3 g(gridForPairs(nItems)), b(QA_BLOCK);
-    if (mode < 0) {
-        hipLaunchKernelGGL((k_pauli_apply_diag<R, FIRST>), g, b, 0, stream, psi, dest, a, ident, nItems);
-    } else if constexpr (sizeof(R) == 4) {
-        if (mode == 2) {
-            hipLaunchKernelGGL(
-                (k_pauli_apply<R, 2, FIRST>), g, b, 0, stream, psi, dest, a, ident, nItems, topPow);
-        } else {
-            hipLaunchKernelGGL(
-                (k_pauli_apply<R, 1, FIRST>), g, b, 0, stream, psi, dest, a, ident, nItems, topPow);
-        }
-    } else {
-        hipLaunchKernelGGL((k_pauli_apply<R, 0, FIRST>), g, b, 0, stream, psi, dest, a, ident, nItems, topPow);
+        pauliApplyDiagItem<R, FIRST, false>(psi, nullptr, dest, a, ident, 0.0, v, unused);
     }
 }
 
@@ -4845,19 +4788,27 @@ template <typename R>
 void launchPauliApply(const cplx<R>* psi, cplx<R>* dest, const PauliArgs& a, double ident, bool first,
     hipStream_t stream)
 {
-    if (first) {
-        launchPauliApplyFirst<R, true>(psi, dest, a, ident, stream);
-    } else {
-        launchPauliApplyFirst<R, false>(psi, dest, a, 0.0, stream);
-    }
+    pauliPairDispatch<R>(a.x, a.nAmps, [&](auto mode, bitCapInt nItems, bitCapInt topPow) {
+        liftBool(first, [&](auto fs) {
+            constexpr int MODE = decltype(mode)::value;
+            constexpr bool FIRST = decltype(fs)::value;
+            const double id = FIRST ? ident : 0.0;
+            const dim3 g(gridForPairs(nItems)), b(QA_BLOCK);
+            if constexpr (MODE < 0) {
+                hipLaunchKernelGGL((k_pauli_apply_diag<R, FIRST>), g, b, 0, stream, psi, dest, a, id, nItems);
+            } else {
+                hipLaunchKernelGGL(
+                    (k_pauli_apply<R, MODE, FIRST>), g, b, 0, stream, psi, dest, a, id, nItems, topPow);
+            }
+        });
+    });
 }
 
-// sign of the one string at index i (and at i + 1 when TWO): parity of i & z
-template <bool TWO>
-__device__ __forceinline__ void pauliAdjointParity(bitCapInt z, bitCapInt i, unsigned& p0, unsigned& p1)
+// p[l]: parity of (i + l) & z, the sign of the one string at that index
+template <int L> __device__ __forceinline__ void pauliAdjointParity(bitCapInt z, bitCapInt i, unsigned (&p)[L])
 {
-    p0 = __popcll(i & z) & 1u;
-    p1 = TWO ? (p0 ^ (unsigned)(z & 1u)) : 0u;
+    p[0] = __popcll(i & z) & 1u;
+    if constexpr (L == 2) p[1] = p[0] ^ (unsigned)(z & 1u);
 }
 
 // One step of the adjoint sweep for a trainable rotation exp(-i theta P): sum
@@ -4869,75 +4820,30 @@ template <typename R, int MODE, bool NT>
 __global__ void k_pauli_adjoint(cplx<R>* psi, cplx<R>* lam, PauliAdjointArgs a, bitCapInt nItems,
     bitCapInt topPow, double* partialsRe, double* partialsIm)
 {
+    using Item = PairItem<R, MODE>;
+    constexpr int L = Item::L;
     double re = 0, im = 0;
     const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
     const bool isIm = a.im != 0;
     const R c = (R)a.cs, s = (R)a.sn;
     for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        unsigned p0, p1;
-        if constexpr (MODE == 0) {
-            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
-            double2* ps = reinterpret_cast<double2*>(psi);
-            double2* pl = reinterpret_cast<double2*>(lam);
-            double2 A = ps[i], B = ps[i ^ a.x], P = pl[i], Q = pl[i ^ a.x];
-            pauliAdjointParity<false>(a.z, i, p0, p1);
-            const double w = p0 ? -a.w : a.w;
-            pauliBraketPair<double>(
-                A.x, A.y, B.x, B.y, P.x, P.y, Q.x, Q.y, isIm ? 0.0 : w, isIm ? w : 0.0, re, im);
-            const double s0 = p0 ? -s : s;
-            pauliEvolveRot<double>(isIm, c, s0, A.x, A.y, B.x, B.y);
-            pauliEvolveRot<double>(isIm, c, s0, P.x, P.y, Q.x, Q.y);
-            ps[i] = A;
-            ps[i ^ a.x] = B;
-            pl[i] = P;
-            pl[i ^ a.x] = Q;
-        } else if constexpr (MODE == 1) {
-            const bitCapInt j = v << 1u;
-            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
-            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
-            float4* ps = reinterpret_cast<float4*>(psi);
-            float4* pl = reinterpret_cast<float4*>(lam);
-            float4 A = ld4<NT>(ps + ia), B = ld4<NT>(ps + ib);
-            float4 P = ld4<NT>(pl + ia), Q = ld4<NT>(pl + ib);
-            const bool swapped = (a.x & 1u) != 0;
-            if (swapped) {
-                B = make_float4(B.z, B.w, B.x, B.y);
-                Q = make_float4(Q.z, Q.w, Q.x, Q.y);
-            }
-            pauliAdjointParity<true>(a.z, i, p0, p1);
-            const double w0 = p0 ? -a.w : a.w, w1 = p1 ? -a.w : a.w;
-            pauliBraketPair<float>(
-                A.x, A.y, B.x, B.y, P.x, P.y, Q.x, Q.y, isIm ? 0.0 : w0, isIm ? w0 : 0.0, re, im);
-            pauliBraketPair<float>(
-                A.z, A.w, B.z, B.w, P.z, P.w, Q.z, Q.w, isIm ? 0.0 : w1, isIm ? w1 : 0.0, re, im);
-            const float s0 = p0 ? -s : s, s1 = p1 ? -s : s;
-            pauliEvolveRot<float>(isIm, c, s0, A.x, A.y, B.x, B.y);
-            pauliEvolveRot<float>(isIm, c, s1, A.z, A.w, B.z, B.w);
-            pauliEvolveRot<float>(isIm, c, s0, P.x, P.y, Q.x, Q.y);
-            pauliEvolveRot<float>(isIm, c, s1, P.z, P.w, Q.z, Q.w);
-            if (swapped) {
-                B = make_float4(B.z, B.w, B.x, B.y);
-                Q = make_float4(Q.z, Q.w, Q.x, Q.y);
-            }
-            st4<NT>(ps + ia, A);
-            st4<NT>(ps + ib, B);
-            st4<NT>(pl + ia, P);
-            st4<NT>(pl + ib, Q);
-        } else {
-            const bitCapInt i = v << 1u;
-            float4* ps = reinterpret_cast<float4*>(psi);
-            float4* pl = reinterpret_cast<float4*>(lam);
-            float4 A = ld4<NT>(ps + v), P = ld4<NT>(pl + v);
-            pauliAdjointParity<false>(a.z, i, p0, p1);
-            const double w = p0 ? -a.w : a.w;
-            pauliBraketPair<float>(
-                A.x, A.y, A.z, A.w, P.x, P.y, P.z, P.w, isIm ? 0.0 : w, isIm ? w : 0.0, re, im);
-            const float s0 = p0 ? -s : s;
-            pauliEvolveRot<float>(isIm, c, s0, A.x, A.y, A.z, A.w);
-            pauliEvolveRot<float>(isIm, c, s0, P.x, P.y, P.z, P.w);
-            st4<NT>(ps + v, A);
-            st4<NT>(pl + v, P);
-        }
+        const Item it(v, topPow, a.x);
+        cplx<R> A[L], B[L], P[L], Q[L];
+        unsigned p[L];
+        double w[L];
+        R sl[L];
+        it.template load<NT>(psi, A, B);
+        it.template load<NT>(lam, P, Q);
+        pauliAdjointParity(a.z, it.i, p);
+        forLanes<L>([&](auto l) { w[l] = p[l] ? -a.w : a.w; });
+        forLanes<L>([&](auto l) {
+            pauliBraketPair(A[l], B[l], P[l], Q[l], isIm ? 0.0 : w[l], isIm ? w[l] : 0.0, re, im);
+        });
+        forLanes<L>([&](auto l) { sl[l] = p[l] ? -s : s; });
+        forLanes<L>([&](auto l) { pauliEvolveRot(isIm, c, sl[l], A[l], B[l]); });
+        forLanes<L>([&](auto l) { pauliEvolveRot(isIm, c, sl[l], P[l], Q[l]); });
+        it.template store<NT>(psi, A, B);
+        it.template store<NT>(lam, P, Q);
     }
     blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
 }
@@ -4947,79 +4853,52 @@ template <typename R, bool NT>
 __global__ void k_pauli_adjoint_diag(cplx<R>* psi, cplx<R>* lam, PauliAdjointArgs a, bitCapInt nItems,
     double* partialsRe, double* partialsIm)
 {
+    using Item = PairItem<R, -1>;
+    constexpr int L = Item::L;
     double re = 0, im = 0;
     const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
     const R c = (R)a.cs, s = (R)a.sn;
     for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        unsigned p0, p1;
-        if constexpr (sizeof(R) == 4) {
-            float4* ps = reinterpret_cast<float4*>(psi);
-            float4* pl = reinterpret_cast<float4*>(lam);
-            float4 A = ld4<NT>(ps + v), P = ld4<NT>(pl + v);
-            pauliAdjointParity<true>(a.z, v << 1u, p0, p1);
-            pauliBraketDiag<float>(A.x, A.y, P.x, P.y, p0 ? -a.w : a.w, re, im);
-            pauliBraketDiag<float>(A.z, A.w, P.z, P.w, p1 ? -a.w : a.w, re, im);
-            const float s0 = p0 ? -s : s, s1 = p1 ? -s : s;
-            pauliEvolveScale<float>(c, -s0, A.x, A.y);
-            pauliEvolveScale<float>(c, -s1, A.z, A.w);
-            pauliEvolveScale<float>(c, -s0, P.x, P.y);
-            pauliEvolveScale<float>(c, -s1, P.z, P.w);
-            st4<NT>(ps + v, A);
-            st4<NT>(pl + v, P);
-        } else {
-            double2* ps = reinterpret_cast<double2*>(psi);
-            double2* pl = reinterpret_cast<double2*>(lam);
-            double2 A = ps[v], P = pl[v];
-            pauliAdjointParity<false>(a.z, v, p0, p1);
-            pauliBraketDiag<double>(A.x, A.y, P.x, P.y, p0 ? -a.w : a.w, re, im);
-            const double s0 = p0 ? -s : s;
-            pauliEvolveScale<double>(c, -s0, A.x, A.y);
-            pauliEvolveScale<double>(c, -s0, P.x, P.y);
-            ps[v] = A;
-            pl[v] = P;
-        }
+        const Item it(v, 0u, 0u);
+        cplx<R> A[L], P[L];
+        unsigned p[L];
+        R sl[L];
+        it.template load<NT>(psi, A);
+        it.template load<NT>(lam, P);
+        pauliAdjointParity(a.z, it.i, p);
+        forLanes<L>([&](auto l) {
+            pauliBraketDiag(A[l], P[l], p[l] ? -a.w : a.w, re, im);
+            sl[l] = p[l] ? s : -s; // minus the pair kernel's signed sine: e^{-i angle}
+        });
+        forLanes<L>([&](auto l) { pauliEvolveScale(c, sl[l], A[l]); });
+        forLanes<L>([&](auto l) { pauliEvolveScale(c, sl[l], P[l]); });
+        it.template store<NT>(psi, A);
+        it.template store<NT>(lam, P);
     }
     blockSumStore2(re, im, partialsRe + blockIdx.x, partialsIm + blockIdx.x);
-}
-
-template <typename R, bool NT>
-static void launchPauliAdjointNt(cplx<R>* psi, cplx<R>* lam, const PauliAdjointArgs& a, double* partialsDev,
-    double* resultDev, hipStream_t stream)
-{
-    bitCapInt nItems, topPow;
-    const int mode = pauliPairMode<R>(a.x, a.nAmps, nItems, topPow);
-    const int grid = gridForPairs(nItems);
-    double* pRe = partialsDev;
-    double* pIm = partialsDev + QA_REDUCE_MAX_BLOCKS;
-    const dim3 g(grid), b(QA_BLOCK);
-    if (mode < 0) {
-        hipLaunchKernelGGL((k_pauli_adjoint_diag<R, NT>), g, b, 0, stream, psi, lam, a, nItems, pRe, pIm);
-    } else if constexpr (sizeof(R) == 4) {
-        if (mode == 2) {
-            hipLaunchKernelGGL(
-                (k_pauli_adjoint<R, 2, NT>), g, b, 0, stream, psi, lam, a, nItems, topPow, pRe, pIm);
-        } else {
-            hipLaunchKernelGGL(
-                (k_pauli_adjoint<R, 1, NT>), g, b, 0, stream, psi, lam, a, nItems, topPow, pRe, pIm);
-        }
-    } else {
-        hipLaunchKernelGGL((k_pauli_adjoint<R, 0, NT>), g, b, 0, stream, psi, lam, a, nItems, topPow, pRe, pIm);
-    }
-    hipLaunchKernelGGL(k_pauli_finish2, dim3(1), dim3(QA_BLOCK), 0, stream, pRe, pIm, grid, resultDev);
 }
 
 template <typename R>
 void launchPauliAdjoint(cplx<R>* psi, cplx<R>* lam, const PauliAdjointArgs& a, double* partialsDev,
     double* resultDev, hipStream_t stream)
 {
-    // nontemporal access exists for the float4 streams only
-    if constexpr (sizeof(R) == 4) {
-        if (useNontemporal()) {
-            launchPauliAdjointNt<R, true>(psi, lam, a, partialsDev, resultDev, stream);
-            return;
-        }
-    }
-    launchPauliAdjointNt<R, false>(psi, lam, a, partialsDev, resultDev, stream);
+    double* pRe = partialsDev;
+    double* pIm = partialsDev + QA_REDUCE_MAX_BLOCKS;
+    pauliPairDispatch<R>(a.x, a.nAmps, [&](auto mode, bitCapInt nItems, bitCapInt topPow) {
+        liftBool<sizeof(R) == 4>(useNontemporal(), [&](auto nt) {
+            constexpr int MODE = decltype(mode)::value;
+            constexpr bool NT = decltype(nt)::value;
+            const int grid = gridForPairs(nItems);
+            const dim3 g(grid), b(QA_BLOCK);
+            if constexpr (MODE < 0) {
+                hipLaunchKernelGGL((k_pauli_adjoint_diag<R, NT>), g, b, 0, stream, psi, lam, a, nItems, pRe, pIm);
+            } else {
+                hipLaunchKernelGGL(
+                    (k_pauli_adjoint<R, MODE, NT>), g, b, 0, stream, psi, lam, a, nItems, topPow, pRe, pIm);
+            }
+            hipLaunchKernelGGL(k_pauli_finish2, dim3(1), b, 0, stream, pRe, pIm, grid, resultDev);
+        });
+    });
 }
 
 // ---- Krylov: fused Lanczos step, basis combination ----------------------------------
@@ -5027,22 +4906,12 @@ void launchPauliAdjoint(cplx<R>* psi, cplx<R>* lam, const PauliAdjointArgs& a, d
 // One Lanczos step (krylov.hpp) on the unnormalised basis is
 //   w = s H u - b prev,  A = Re <u|w>,  w <- w - s^2 A u,  ||w||^2
 // with s and b folded into the weight table, ident and bcoef by the host. The
-// apply kernels are k_pauli_apply with two additions: every pair adds its
-// share 2 Re(W conj(u[j]) u[i]) of A as a double partial (both amplitudes are
-// in registers already), and the FIRST form, which writes dest without reading
-// it, also takes - bcoef * prev from a third stream (prev == nullptr: none).
+// apply kernels are the KRYLOV form of k_pauli_apply's item: every pair adds
+// its share of A as a double partial (both amplitudes are in registers
+// already), and the FIRST form also takes - bcoef * prev.
 // Each launch's block partials fold on the device into a slot of its own;
 // k_krylov_finish reads the slots back, so A never visits the host before w is
 // final. No atomics anywhere: every sum has a fixed order.
-
-// (re, im) of a - c p for one amplitude, and the share - c Re(conj(a) p) of A
-template <typename R>
-__device__ __forceinline__ void krylovPrev(R ar, R ai, R pr, R pi, R c, double cd, R& dr, R& di, double& s)
-{
-    dr -= c * pr;
-    di -= c * pi;
-    s -= cd * (double)(ar * pr + ai * pi);
-}
 
 template <typename R, int MODE, bool FIRST>
 __global__ void k_krylov_apply(const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, PauliArgs a,
@@ -5050,199 +4919,46 @@ __global__ void k_krylov_apply(const cplx<R>* u, const cplx<R>* prev, cplx<R>* d
 {
     double s = 0;
     const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
-    const R id = (R)ident, bc = (R)bcoef;
     for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        double wr0, wr1, wi0, wi1;
-        if constexpr (MODE == 0) {
-            const bitCapInt i = ((v & ~(topPow - 1u)) << 1u) | (v & (topPow - 1u));
-            const double2 A = reinterpret_cast<const double2*>(u)[i];
-            const double2 B = reinterpret_cast<const double2*>(u)[i ^ a.x];
-            double2* d = reinterpret_cast<double2*>(dest);
-            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            s += pauliPair<double>(A.x, A.y, B.x, B.y, wr0, wi0);
-            double2 DA, DB;
-            if constexpr (FIRST) {
-                DA = make_double2(id * A.x, id * A.y);
-                DB = make_double2(id * B.x, id * B.y);
-                s += ident * ((A.x * A.x + A.y * A.y) + (B.x * B.x + B.y * B.y));
-                if (prev) {
-                    const double2 P = reinterpret_cast<const double2*>(prev)[i];
-                    const double2 Q = reinterpret_cast<const double2*>(prev)[i ^ a.x];
-                    krylovPrev<double>(A.x, A.y, P.x, P.y, bc, bcoef, DA.x, DA.y, s);
-                    krylovPrev<double>(B.x, B.y, Q.x, Q.y, bc, bcoef, DB.x, DB.y, s);
-                }
-            } else {
-                DA = d[i];
-                DB = d[i ^ a.x];
-            }
-            pauliApplyMad<double>(wr0, -wi0, B.x, B.y, DA.x, DA.y);
-            pauliApplyMad<double>(wr0, wi0, A.x, A.y, DB.x, DB.y);
-            d[i] = DA;
-            d[i ^ a.x] = DB;
-        } else if constexpr (MODE == 1) {
-            const bitCapInt j = v << 1u;
-            const bitCapInt i = ((j & ~(topPow - 1u)) << 1u) | (j & (topPow - 1u));
-            const bitCapInt ia = i >> 1u, ib = (i ^ a.x) >> 1u;
-            const float4 A = reinterpret_cast<const float4*>(u)[ia];
-            float4 B = reinterpret_cast<const float4*>(u)[ib];
-            float4* d = reinterpret_cast<float4*>(dest);
-            const bool swapped = (a.x & 1u) != 0;
-            if (swapped) B = make_float4(B.z, B.w, B.x, B.y);
-            pauliWeights<true>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<true>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            s += pauliPair<float>(A.x, A.y, B.x, B.y, wr0, wi0);
-            s += pauliPair<float>(A.z, A.w, B.z, B.w, wr1, wi1);
-            float4 DA, DB;
-            if constexpr (FIRST) {
-                DA = make_float4(id * A.x, id * A.y, id * A.z, id * A.w);
-                DB = make_float4(id * B.x, id * B.y, id * B.z, id * B.w);
-                s += ident
-                    * (((double)(A.x * A.x + A.y * A.y) + (double)(A.z * A.z + A.w * A.w))
-                        + ((double)(B.x * B.x + B.y * B.y) + (double)(B.z * B.z + B.w * B.w)));
-                if (prev) {
-                    const float4 P = reinterpret_cast<const float4*>(prev)[ia];
-                    float4 Q = reinterpret_cast<const float4*>(prev)[ib];
-                    if (swapped) Q = make_float4(Q.z, Q.w, Q.x, Q.y);
-                    krylovPrev<float>(A.x, A.y, P.x, P.y, bc, bcoef, DA.x, DA.y, s);
-                    krylovPrev<float>(A.z, A.w, P.z, P.w, bc, bcoef, DA.z, DA.w, s);
-                    krylovPrev<float>(B.x, B.y, Q.x, Q.y, bc, bcoef, DB.x, DB.y, s);
-                    krylovPrev<float>(B.z, B.w, Q.z, Q.w, bc, bcoef, DB.z, DB.w, s);
-                }
-            } else {
-                DA = d[ia];
-                DB = d[ib];
-                if (swapped) DB = make_float4(DB.z, DB.w, DB.x, DB.y);
-            }
-            pauliApplyMad<float>((float)wr0, -(float)wi0, B.x, B.y, DA.x, DA.y);
-            pauliApplyMad<float>((float)wr1, -(float)wi1, B.z, B.w, DA.z, DA.w);
-            pauliApplyMad<float>((float)wr0, (float)wi0, A.x, A.y, DB.x, DB.y);
-            pauliApplyMad<float>((float)wr1, (float)wi1, A.z, A.w, DB.z, DB.w);
-            if (swapped) DB = make_float4(DB.z, DB.w, DB.x, DB.y);
-            d[ia] = DA;
-            d[ib] = DB;
-        } else {
-            const bitCapInt i = v << 1u;
-            const float4 A = reinterpret_cast<const float4*>(u)[v];
-            float4* d = reinterpret_cast<float4*>(dest);
-            pauliWeights<false>(a, 0, a.nRe, i, wr0, wr1);
-            pauliWeights<false>(a, a.nRe, a.nTerms, i, wi0, wi1);
-            s += pauliPair<float>(A.x, A.y, A.z, A.w, wr0, wi0);
-            float4 D;
-            if constexpr (FIRST) {
-                D = make_float4(id * A.x, id * A.y, id * A.z, id * A.w);
-                s += ident * ((double)(A.x * A.x + A.y * A.y) + (double)(A.z * A.z + A.w * A.w));
-                if (prev) {
-                    const float4 P = reinterpret_cast<const float4*>(prev)[v];
-                    krylovPrev<float>(A.x, A.y, P.x, P.y, bc, bcoef, D.x, D.y, s);
-                    krylovPrev<float>(A.z, A.w, P.z, P.w, bc, bcoef, D.z, D.w, s);
-                }
-            } else {
-                D = d[v];
-            }
-            pauliApplyMad<float>((float)wr0, -(float)wi0, A.z, A.w, D.x, D.y);
-            pauliApplyMad<float>((float)wr0, (float)wi0, A.x, A.y, D.z, D.w);
-            d[v] = D;
-        }
+        pauliApplyItem<R, MODE, FIRST, true>(u, prev, dest, a, ident, bcoef, v, topPow, s);
     }
     blockSumStore(s, partials + blockIdx.x);
 }
 
-// x == 0: dest[i] (+)= W(i) u[i], share W(i) |u[i]|^2; FIRST as above
 template <typename R, bool FIRST>
 __global__ void k_krylov_apply_diag(const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, PauliArgs a,
     double ident, double bcoef, bitCapInt nItems, double* partials)
 {
     double s = 0;
     const bitCapInt stride = (bitCapInt)gridDim.x * blockDim.x;
-    const R bc = (R)bcoef;
     for (bitCapInt v = (bitCapInt)blockIdx.x * blockDim.x + threadIdx.x; v < nItems; v += stride) {
-        double w0, w1;
-        if constexpr (sizeof(R) == 4) {
-            const float4 A = reinterpret_cast<const float4*>(u)[v];
-            float4* d = reinterpret_cast<float4*>(dest);
-            pauliWeights<true>(a, 0, a.nTerms, v << 1u, w0, w1);
-            if constexpr (FIRST) {
-                w0 += ident;
-                w1 += ident;
-            }
-            s += w0 * (double)(A.x * A.x + A.y * A.y) + w1 * (double)(A.z * A.z + A.w * A.w);
-            const float f0 = (float)w0, f1 = (float)w1;
-            float4 D;
-            if constexpr (FIRST) {
-                D = make_float4(f0 * A.x, f0 * A.y, f1 * A.z, f1 * A.w);
-                if (prev) {
-                    const float4 P = reinterpret_cast<const float4*>(prev)[v];
-                    krylovPrev<float>(A.x, A.y, P.x, P.y, bc, bcoef, D.x, D.y, s);
-                    krylovPrev<float>(A.z, A.w, P.z, P.w, bc, bcoef, D.z, D.w, s);
-                }
-            } else {
-                D = d[v];
-                D.x += f0 * A.x;
-                D.y += f0 * A.y;
-                D.z += f1 * A.z;
-                D.w += f1 * A.w;
-            }
-            d[v] = D;
-        } else {
-            const double2 A = reinterpret_cast<const double2*>(u)[v];
-            double2* d = reinterpret_cast<double2*>(dest);
-            pauliWeights<false>(a, 0, a.nTerms, v, w0, w1);
-            if constexpr (FIRST) w0 += ident;
-            s += w0 * (A.x * A.x + A.y * A.y);
-            double2 D;
-            if constexpr (FIRST) {
-                D = make_double2(w0 * A.x, w0 * A.y);
-                if (prev) {
-                    const double2 P = reinterpret_cast<const double2*>(prev)[v];
-                    krylovPrev<double>(A.x, A.y, P.x, P.y, bc, bcoef, D.x, D.y, s);
-                }
-            } else {
-                D = d[v];
-                D.x += w0 * A.x;
-                D.y += w0 * A.y;
-            }
-            d[v] = D;
-        }
+        pauliApplyDiagItem<R, FIRST, true>(u, prev, dest, a, ident, bcoef, v, s);
     }
     blockSumStore(s, partials + blockIdx.x);
-}
-
-template <typename R, bool FIRST>
-static void launchKrylovApplyFirst(const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, const PauliArgs& a,
-    double ident, double bcoef, double* partialsDev, double* slotDev, hipStream_t stream)
-{
-    bitCapInt nItems, topPow;
-    const int mode = pauliPairMode<R>(a.x, a.nAmps, nItems, topPow);
-    const int grid = gridForPairs(nItems);
-    const dim3 g(grid), b(QA_BLOCK);
-    if (mode < 0) {
-        hipLaunchKernelGGL((k_krylov_apply_diag<R, FIRST>), g, b, 0, stream, u, prev, dest, a, ident, bcoef,
-            nItems, partialsDev);
-    } else if constexpr (sizeof(R) == 4) {
-        if (mode == 2) {
-            hipLaunchKernelGGL((k_krylov_apply<R, 2, FIRST>), g, b, 0, stream, u, prev, dest, a, ident, bcoef,
-                nItems, topPow, partialsDev);
-        } else {
-            hipLaunchKernelGGL((k_krylov_apply<R, 1, FIRST>), g, b, 0, stream, u, prev, dest, a, ident, bcoef,
-                nItems, topPow, partialsDev);
-        }
-    } else {
-        hipLaunchKernelGGL((k_krylov_apply<R, 0, FIRST>), g, b, 0, stream, u, prev, dest, a, ident, bcoef,
-            nItems, topPow, partialsDev);
-    }
-    hipLaunchKernelGGL(k_pauli_finish, dim3(1), dim3(QA_BLOCK), 0, stream, partialsDev, grid, slotDev);
 }
 
 template <typename R>
 void launchKrylovApply(const cplx<R>* u, const cplx<R>* prev, cplx<R>* dest, const PauliArgs& a, double ident,
     double bcoef, bool first, double* partialsDev, double* slotDev, hipStream_t stream)
 {
-    if (first) {
-        launchKrylovApplyFirst<R, true>(u, prev, dest, a, ident, bcoef, partialsDev, slotDev, stream);
-    } else {
-        launchKrylovApplyFirst<R, false>(u, nullptr, dest, a, 0.0, 0.0, partialsDev, slotDev, stream);
-    }
+    pauliPairDispatch<R>(a.x, a.nAmps, [&](auto mode, bitCapInt nItems, bitCapInt topPow) {
+        liftBool(first, [&](auto fs) {
+            constexpr int MODE = decltype(mode)::value;
+            constexpr bool FIRST = decltype(fs)::value;
+            const cplx<R>* pv = FIRST ? prev : nullptr;
+            const double id = FIRST ? ident : 0.0, bc = FIRST ? bcoef : 0.0;
+            const int grid = gridForPairs(nItems);
+            const dim3 g(grid), b(QA_BLOCK);
+            if constexpr (MODE < 0) {
+                hipLaunchKernelGGL((k_krylov_apply_diag<R, FIRST>), g, b, 0, stream, u, pv, dest, a, id, bc,
+                    nItems, partialsDev);
+            } else {
+                hipLaunchKernelGGL((k_krylov_apply<R, MODE, FIRST>), g, b, 0, stream, u, pv, dest, a, id, bc,
+                    nItems, topPow, partialsDev);
+            }
+            hipLaunchKernelGGL(k_pauli_finish, dim3(1), b, 0, stream, partialsDev, grid, slotDev);
+        });
+    });
 }
 
 // w <- w - a u with a = scale * (sum of the step's slots), and the block's

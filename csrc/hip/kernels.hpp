@@ -201,9 +201,13 @@ template <typename R>
 void launchPauliGroup(const cplx<R>* sv, const PauliArgs& a, double* partialsDev,
     double* resultDev, hipStream_t stream);
 
-// The three pair-walk launches below use the reduction grid, capped by
-// QRACK_GPU_BLOCKS when that is set. partialsDev holds 2 * QA_REDUCE_MAX_BLOCKS
-// doubles (real parts, then imaginary parts); resultDev takes (re, im).
+// Every pair-walk launch that reduces (launchPauliGroup above, the launches
+// below and launchKrylovApply) uses the reduction grid, capped by
+// QRACK_GPU_BLOCKS when that is set; launchPauliApply uses the same grid and
+// launchPauliEvolve the exact streaming grid under the same cap. For the
+// complex results of launchPauliBraket and launchPauliAdjoint partialsDev
+// holds 2 * QA_REDUCE_MAX_BLOCKS doubles (real parts, then imaginary parts)
+// and resultDev takes (re, im).
 
 // <bra| ident + sum_t w_t P_t |psi> for one group; reads both vectors only
 template <typename R>

@@ -306,6 +306,77 @@ def test_grid_stride_product_state(n):
     assert abs(q.expectation_pauli_sum(zz) - want) <= 2e-4 * len(zz)
 
 
+def stride_cases():
+    """(x, strings, weighted terms) for x == 0 and every mask of x_masks_12()"""
+    diag = [([0], [2]), ([N12 - 1], [2]), ([0, N12 - 1], [2, 2]), ([5, 6, 7, 8], [2] * 4),
+            (list(range(N12)), [2] * N12)]
+    out = []
+    for x in [0] + x_masks_12():
+        strings = strings_for_mask(x) if x else diag
+        rng = np.random.default_rng(500 + x)
+        out.append((x, strings, [(float(rng.uniform(-1, 1)), qs, ps) for qs, ps in strings]))
+    return out
+
+
+def stride_mixed_terms():
+    rng = np.random.default_rng(81)
+    terms = []
+    for x in (0, 1, 0x801, 0x1e0):
+        terms += terms_sharing_x(x, 10, rng)
+    return [terms[i] for i in rng.permutation(len(terms))]
+
+
+def child_stride_values(path):
+    """run by the child under QRACK_GPU_BLOCKS=2: per string, per group and mixed-sum values"""
+    out = {}
+    for prec in PRECS:
+        q, sv, _ = hip_with_state(N12, prec, 1200)
+        out[f"{prec}_sv"] = sv
+        for x, strings, terms in stride_cases():
+            vals = [q.pauli_expectation(qs, ps) for qs, ps in strings]
+            out[f"{prec}_{x}"] = np.array(vals + [q.expectation_pauli_sum(terms)])
+        mixed = stride_mixed_terms()
+        out[f"{prec}_mixed"] = np.array([q.expectation_pauli_sum(mixed), q.expectation_pauli_sum(mixed)])
+    np.savez(path, **out)
+
+
+_CHILD_STRIDE = r"""
+import os, sys
+sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import test_pauli_sum_gpu as t
+t.child_stride_values(sys.argv[2])
+print("CHILD_OK")
+"""
+
+
+def test_stride_loop_in_child(tmp_path):
+    """QRACK_GPU_BLOCKS=2 (read once per process) leaves 512 threads for the
+    1024 items of the fp32 two-pair stream and the 2048 or more of every other
+    one, so at 12 qubits each addressing mode takes a second trip."""
+    path = str(tmp_path / "values.npz")
+    r = subprocess.run(
+        [sys.executable, "-c", _CHILD_STRIDE, ROOT, path],
+        env={**os.environ, "QRACK_GPU_BLOCKS": "2"}, capture_output=True, text=True, timeout=300,
+    )
+    assert r.returncode == 0 and "CHILD_OK" in r.stdout, f"stdout={r.stdout}\nstderr={r.stderr}"
+    data = np.load(path)
+    for prec in PRECS:
+        sv = data[f"{prec}_sv"]
+        for x, strings, terms in stride_cases():
+            vals = data[f"{prec}_{x}"]
+            assert len(vals) == len(strings) + 1
+            assert {po.masks(qs, ps)[0] for qs, ps in strings} == {x}
+            for got, (qs, ps) in zip(vals, strings):
+                assert abs(got - po.expect(sv, qs, ps)) <= TOL[prec], (prec, qs, ps)
+            assert abs(vals[-1] - po.expect_sum(sv, terms)) <= TOL[prec] * po.abs_coeffs(terms), (prec, x)
+        mixed = stride_mixed_terms()
+        assert len(mixed) == 40 and len({po.masks(qs, ps)[0] for _, qs, ps in mixed}) == 4
+        a, b = data[f"{prec}_mixed"]
+        assert a.tobytes() == b.tobytes()  # fixed reduction order: bit-identical
+        assert abs(a - po.expect_sum(sv, mixed)) <= TOL[prec] * po.abs_coeffs(mixed), prec
+
+
 # ---- 6. through layers ---------------------------------------------------------------
 
 
